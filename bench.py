@@ -10,6 +10,19 @@ batched objective, sort, mean/paths, rank-μ covariance update, σ update.
 Everything runs on the device; the host only enqueues.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--cov exact|mfma]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up,
+warms up, times the K steps, writes the outputs of the last timed step when
+--dump-outputs DIR is given (DIR/<name>.npy, float64 / float32, at most 64 MB
+in all; the same arguments give the same inputs, so two builds compare output
+for output) and prints the JSON line.  Everything else described below (the
+per-stage pass and the rooflines, the engine rates, the other covariance
+mode, the `c4_sharded` and `c1` sub-lines, the CPU baselines) takes runs of
+its own and is measured with --full only.  Every run first confines itself
+to the CPUs of one L3 domain (confine_to_l3: the host threads of a generation
+hand off to each other, and a run whose threads the scheduler had spread over
+two domains measured 40% slower than the next); `config.host_cpus` names them.
 
 N > 1: one process per GPU — launched by torch.distributed.run (RANK /
 WORLD_SIZE set), or, when WORLD_SIZE is unset, bench.py starts the N rank
@@ -17,12 +30,12 @@ processes itself before touching the GPU.  Every rank runs its own C2
 experiment (seed 1337 + rank) — "replicas", weak scaling, no collective on
 the data path (λ = 4096 fits one GPU many times over; DESIGN.md §6);
 value = total generations/s over all ranks (max-over-ranks wall time).
-Beside it, `c4_sharded`: the C4 experiment (512-dim Ackley, λ = 65536)
+Beside it (--full), `c4_sharded`: the C4 experiment (512-dim Ackley, λ = 65536)
 through korali.Engine on one rank and sharded over all N ranks (the
 Distributed conduit, exact covariance order), its rates and speed-up, and
 whether the two runs ended bit-identical.
 
-The JSON line also carries `roofline` for the dominant kernel (algorithmic
+With --full the JSON line also carries `roofline` for the dominant kernel (algorithmic
 FLOPs per launch / its HIP-event time on the solver's stream) and
 `cpu_baseline` (the bit-exact CPU oracle, one core, bounded sample).
 """
@@ -373,6 +386,68 @@ def progress(msg):
     print(f"[bench {time.perf_counter() - _T_START:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+def confine_to_l3():
+    """Keep this process on the CPUs that share the L3 cache of the core it
+    runs on (what `taskset -c <those cpus> python bench.py` does), before the
+    library starts a thread.  The library pins its tridiagonalisation helpers
+    next to the thread that creates the solver, but that thread and the
+    eigensolver's worker stay free to migrate; whenever the scheduler moved one
+    of them to another L3 domain a C2 generation took 0.75 ms instead of
+    0.53 ms (every hand-off crossing the domains), for seconds at a time or
+    for a whole run, so equal runs differed by 40%.  Returns the CPUs, or None
+    where the topology cannot be read (the process is left as it is)."""
+    try:
+        import ctypes
+        cpu = ctypes.CDLL(None, use_errno=True).sched_getcpu()
+        cpus = set()
+        with open(f"/sys/devices/system/cpu/cpu{cpu}/cache/index3/shared_cpu_list") as f:
+            for part in f.read().strip().split(","):
+                lo, _, hi = part.partition("-")
+                cpus.update(range(int(lo), int(hi or lo) + 1))
+        cpus &= os.sched_getaffinity(0)
+        if cpu not in cpus:
+            return None
+        os.sched_setaffinity(0, cpus)
+        return sorted(cpus)
+    except (OSError, ValueError, AttributeError):
+        return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write what the timed path computed in its last step,
+    one DIR/<name>.npy per array, float32 kept and everything else as float64.
+    All files together stay under 64 MB: every array gets an equal share, and
+    one that exceeds it is cut to a fixed, seeded sample of its rows (the same
+    rows in every run)."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 256  # (256: the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, share // (a.shape[1] * a.itemsize))
+            rows = np.sort(np.random.default_rng(20240229).choice(a.shape[0], size=keep, replace=False))
+            a = np.ascontiguousarray(a[rows])
+        np.save(os.path.join(directory, name.lower().replace(" ", "_") + ".npy"), a)
+
+
+# the solver state a caller of kg_cmaes_generation reads back after a generation
+CMAES_OUTPUTS = ("Sample Population", "Value Vector", "Current Mean", "Covariance Matrix",
+                 "Covariance Eigenvector Matrix", "Axis Lengths", "Sigma", "Evolution Path",
+                 "Conjugate Evolution Path", "Best Ever Value", "Best Ever Variables")
+
+
+def cmaes_outputs(dev, N):
+    out = {k: dev[k] for k in CMAES_OUTPUTS}
+    for k in ("Sample Population", "Covariance Matrix", "Covariance Eigenvector Matrix"):
+        out[k] = out[k].reshape(-1, N)
+    return out
+
+
 C1_N, C1_LAMBDA, C1_GENS = 8, 16, 1000
 
 
@@ -564,15 +639,23 @@ def main():
     ap.add_argument("--cov", default="exact", choices=["exact", "mfma"],
                     help="exact (default): bit-exact rank-mu order, the reference's trajectory; mfma: FP64 matrix "
                          "cores, <= 1e-12 per step (reported beside the exact rate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c1", action="store_true", help="skip the C1 line (profiling runs: keeps the C2 kernels' "
-                                                        "statistics free of the N=8 launches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float64 / float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-stage times and rooflines, engine "
+                         "rates, the other covariance mode, the c4_sharded and c1 sub-lines, the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-c1", action="store_true", help="with --full: skip the C1 line (profiling runs: keeps the "
+                                                        "C2 kernels' statistics free of the N=8 launches)")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="c2: the BASELINE metric (CMA-ES); c3: TMCMC N=32, P=8192; c4: CMA-ES 512-dim Ackley, "
                          "lambda=65536, population sharded over the ranks; c5: VRACER, 4096 CartPole rollouts")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.workload in ("c2", "c4"):
         sys.exit(spawn_ranks(args.gpus))
+    host_cpus = confine_to_l3()
+    progress("host cpus: " + (",".join(map(str, host_cpus)) if host_cpus else "as inherited"))
     if args.workload in ("c3", "c5") and args.gpus > 1:
         raise SystemExit(f"--workload {args.workload} runs on one GPU (replicas only: start one bench per GPU)")
     if args.workload == "c3":
@@ -631,6 +714,37 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cmaes_outputs(dev, N_VARS))
+    gens_per_s = args.steps * world / elapsed
+    out = {
+        "metric": "CMA-ES generations/sec + samples/sec, 128-dim Rosenbrock λ=4096, 1→8 GPUs",
+        "value": gens_per_s,
+        "unit": "generations/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "C2: CMA-ES, 128-dim negative Rosenbrock, lambda=4096, mu=2048 Logarithmic, "
+                               "x0=0, sigma0=1, seed 1337; one experiment per GPU",
+                   "population": LAMBDA, "variables": N_VARS, "covariance_update": args.cov,
+                   "parallelism": f"replicas{world}", "host_cpus": host_cpus},
+        "samples_per_sec": gens_per_s * LAMBDA,
+    }
+    if not args.full:
+        out["best_ever_value"] = float(dev["Best Ever Value"][0])
+        dev.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # per-stage device times (HIP events on the solver's stream), separate pass
     dev.profile(True)
@@ -694,7 +808,6 @@ def main():
         dist.destroy_process_group()
         return
 
-    gens_per_s = args.steps * world / elapsed
     # rankmu_mfma runs on the second stream, beside mean_paths
     kernels = {k: v for k, v in stages.items() if k not in HOST_STAGES + HOST_FED + ("eigen", "rankmu_mfma")}
     dominant = max(kernels, key=kernels.get)
@@ -709,24 +822,7 @@ def main():
     # n = N-1-i dependent FP64 adds per Householder step at the measured 14
     # shader cycles per add (tools/ubench_chain*.hip), 2.4 GHz
     chain_bound_ms = sum(3 * n for n in range(2, N_VARS)) * 14 / 2.4e9 * 1e3
-    out = {
-        "metric": "CMA-ES generations/sec + samples/sec, 128-dim Rosenbrock λ=4096, 1→8 GPUs",
-        "value": gens_per_s,
-        "unit": "generations/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "C2: CMA-ES, 128-dim negative Rosenbrock, lambda=4096, mu=2048 Logarithmic, "
-                               "x0=0, sigma0=1, seed 1337; one experiment per GPU",
-                   "population": LAMBDA, "variables": N_VARS, "covariance_update": args.cov,
-                   "parallelism": f"replicas{world}"},
-        "samples_per_sec": gens_per_s * LAMBDA,
+    out.update({
         "engine_generations_per_sec": eng,
         "engine_end_to_end_generations_per_sec": eng_e2e,
         "engine_in_run_generations_per_sec": eng_in_run,
@@ -749,7 +845,7 @@ def main():
                      "traffic_raw_fetch": traffic_raw,
                      "traffic_source": profile_file("c2_pmc_traffic.csv")[1] if traffic else None,
                      "algorithmic_flops_per_launch": flops, "avg_launch_ms": dom_ms},
-    }
+    })
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
@@ -759,6 +855,9 @@ def main():
 
 # ----------------------------------------------------------------- C3 TMCMC
 C3_N, C3_P = 32, 8192
+# the sampler state a caller of kg_tmcmc_generation reads back after a generation
+C3_OUTPUTS = ("Sample Database", "Sample LogLikelihood Database", "Chain Leaders", "Chain Leaders LogLikelihoods",
+              "Mean Theta", "Covariance Matrix", "Annealing Exponent", "LogEvidence", "Coefficient Of Variation")
 
 
 def c3_stage_flops(N, P):
@@ -838,8 +937,29 @@ def run_c3(args):
                 break
     exps[min(r, len(exps) - 1)].synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the experiment the last timed generation ran in (a run that had just
+        # ended moved r on to an experiment not yet started)
+        last = exps[r - 1 if g == 0 else min(r, len(exps) - 1)]
+        arrays = {k: last[k] for k in C3_OUTPUTS}
+        for k in ("Chain Leaders", "Sample Database", "Covariance Matrix"):
+            arrays[k] = arrays[k].reshape(-1, C3_N)
+        dump_outputs(args.dump_outputs, arrays)
     for e in exps:
         e.close()
+    out = {
+        "metric": "TMCMC generations/sec, 32-dim Gaussian posterior, P=8192 chains",
+        "value": done / elapsed, "unit": "generations/s", "n_gpus": 1, "steps": done, "warmup": args.warmup,
+        "ms_per_step": elapsed / done * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "C3: TMCMC, 32 variables with one shared U(-5,5) prior, loglik -0.5|x|^2, "
+                               "P=8192, Max Chain Length 1, Target CoV 1.0, Covariance Scaling 0.04; "
+                               "successive runs to annealing exponent 1", "complete_runs": runs},
+        "chain_steps_per_sec": done * C3_P / elapsed,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     # stage times on a fresh run
     dev = c3_experiment(4242)
     dev.profile(True)
@@ -872,15 +992,7 @@ def run_c3(args):
         dominant = max(kernels, key=kernels.get)
     achieved = flops[dominant] / (stages[dominant] * 1e-3) / 1e12
     c3_traffic, _ = pmc_traffic(dominant, "c3_pmc_traffic.csv")
-    out = {
-        "metric": "TMCMC generations/sec, 32-dim Gaussian posterior, P=8192 chains",
-        "value": done / elapsed, "unit": "generations/s", "n_gpus": 1, "steps": done, "warmup": args.warmup,
-        "ms_per_step": elapsed / done * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "C3: TMCMC, 32 variables with one shared U(-5,5) prior, loglik -0.5|x|^2, "
-                               "P=8192, Max Chain Length 1, Target CoV 1.0, Covariance Scaling 0.04; "
-                               "successive runs to annealing exponent 1", "complete_runs": runs},
-        "chain_steps_per_sec": done * C3_P / elapsed,
+    out.update({
         "stage_ms": stages,
         "annealing_search": search,
         "roofline": {"kernel": {"min_search": "kg::k_tm_nm_sym"}.get(dominant, dominant), "stage": dominant,
@@ -892,7 +1004,7 @@ def run_c3(args):
                      "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": c3_traffic,
                      "traffic_source": profile_file("c3_pmc_traffic.csv")[1] if c3_traffic else None,
                      "algorithmic_flops_per_launch": flops[dominant], "avg_launch_ms": stages[dominant]},
-    }
+    })
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = c3_cpu_baseline()
     print(json.dumps(out), flush=True)
@@ -976,6 +1088,20 @@ def run_c4_engine(args, world, rank):
     elapsed = float(t.item())
     best = float(e["Solver"]["Best Ever Value"])
     exch = exchange_ms(e, tdist)
+    if args.dump_outputs and rank == 0:
+        # the solver state the experiment hands back (the 65536 x 512 population
+        # itself is left out: as nested JSON lists it does not fit a benchmark run)
+        arrays = {}
+        for k in CMAES_OUTPUTS:
+            if k == "Sample Population":
+                continue
+            try:
+                arrays[k] = np.asarray(e["Solver"][k], dtype=np.float64).reshape(-1)
+            except (KeyError, TypeError, ValueError):  # (a field this engine build does not publish)
+                continue
+            if arrays[k].size == C4_N * C4_N:
+                arrays[k] = arrays[k].reshape(C4_N, C4_N)
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         print(json.dumps({
             "metric": "CMA-ES generations/sec, 512-dim Ackley lambda=65536 (C4)", "value": args.steps / elapsed,
@@ -989,7 +1115,7 @@ def run_c4_engine(args, world, rank):
             "timing": "generations %d-%d of one %d-generation engine run (engine completion marks), slowest rank"
                       % (w + 1, total, total),
             "exchange_ms_per_generation": exch or None,
-            "cpu_baseline": None if args.no_cpu_baseline else c4_cpu_baseline()}), flush=True)
+            "cpu_baseline": c4_cpu_baseline() if args.full and not args.no_cpu_baseline else None}), flush=True)
     tdist.destroy_process_group()
 
 
@@ -1067,38 +1193,45 @@ def run_c4(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    dev.profile(True)
-    STAGES = ("eigen", "eigen_tridiag", "eigen_publish_c", "eigen_c_wait", "eigen_tridiag_host", "eigen_fetch_h",
-              "eigen_unpack", "eigen_chase_host", "eigen_apply", "rng_polar", "transform",
-              "objective", "sort", "mean_paths", "covariance", "rankmu_mfma", "sigma")
-    for st in ("init",) + STAGES:
-        dev.profile_read(st)
-    for _ in range(2):
-        gen += 1
-        step(gen)
-    dev.synchronize()
-    stages = {}
-    for st in STAGES:
-        ms, n = dev.profile_read(st)
-        if n:
-            stages[st] = ms / n
-    dev.profile(False)
-    best = float(dev["Best Ever Value"][0])
-    if rank == 0:
-        print(json.dumps({
-            "metric": "CMA-ES generations/sec, 512-dim Ackley lambda=65536 (C4)", "value": args.steps / elapsed,
-            "unit": "generations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C4: CMA-ES, 512-dim negative Ackley, lambda=65536, mu=32768 Logarithmic, x0=2, "
-                                   "sigma0=1, seed 1337", "parallelism": f"population-shard{world}",
-                       "covariance_update": args.cov},
-            "samples_per_sec": args.steps / elapsed * C4_L, "best_ever_value": best,
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cmaes_outputs(dev, C4_N))
+    out = {
+        "metric": "CMA-ES generations/sec, 512-dim Ackley lambda=65536 (C4)", "value": args.steps / elapsed,
+        "unit": "generations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "C4: CMA-ES, 512-dim negative Ackley, lambda=65536, mu=32768 Logarithmic, x0=2, "
+                               "sigma0=1, seed 1337", "parallelism": f"population-shard{world}",
+                   "covariance_update": args.cov},
+        "samples_per_sec": args.steps / elapsed * C4_L,
+    }
+    if args.full:
+        dev.profile(True)
+        STAGES = ("eigen", "eigen_tridiag", "eigen_publish_c", "eigen_c_wait", "eigen_tridiag_host", "eigen_fetch_h",
+                  "eigen_unpack", "eigen_chase_host", "eigen_apply", "rng_polar", "transform",
+                  "objective", "sort", "mean_paths", "covariance", "rankmu_mfma", "sigma")
+        for st in ("init",) + STAGES:
+            dev.profile_read(st)
+        for _ in range(2):
+            gen += 1
+            step(gen)
+        dev.synchronize()
+        stages = {}
+        for st in STAGES:
+            ms, n = dev.profile_read(st)
+            if n:
+                stages[st] = ms / n
+        dev.profile(False)
+    out["best_ever_value"] = float(dev["Best Ever Value"][0])
+    if rank == 0 and args.full:
+        out.update({
             "stage_ms_rank0": stages,
             "roofline": c4_roofline(stages),
             "rankmu_mfma_roofline": rankmu_roofline(stages["rankmu_mfma"], C4_L // 2, C4_N, "c4_pmc_traffic.csv")
             if "rankmu_mfma" in stages else None,
-            "cpu_baseline": None if args.no_cpu_baseline else c4_cpu_baseline()}), flush=True)
+            "cpu_baseline": None if args.no_cpu_baseline else c4_cpu_baseline()})
+    if rank == 0:
+        print(json.dumps(out), flush=True)
     solver.close()  # (device memory and the chase thread released before the runtime's teardown)
     if dist is not None:
         dist.destroy_process_group()
@@ -1194,6 +1327,27 @@ def run_c5(args):
         exps, ups = exps + n, ups + u
     d.synchronize()
     elapsed = time.perf_counter() - t0
+    finished = d.get("finished_rewards")
+    if args.dump_outputs:
+        # the trained network and the rollouts' episode returns after the last
+        # timed step, and the policy it gives on a fixed batch of states
+        X = np.random.default_rng(1337).standard_normal((256, 4)).astype(np.float32)
+        dump_outputs(args.dump_outputs, {"hyperparameters": d.hyperparameters, "finished_rewards": finished,
+                                         "policy_states": X, "policy_outputs": d.run_policy(X)})
+    out = {
+        "metric": "VRACER experiences/sec, 4096 concurrent CartPole rollouts, 2x256 policy (C5)",
+        "value": exps / elapsed, "unit": "experiences/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "C5: VRACER Normal policy, CartPole env (examples/learning/reinforcement/cartpole, "
+                               "scipy dopri5 restated), 4096 concurrent environments, 2x256 tanh, mini-batch 256, EBPU 1, "
+                               "replay 262144 (start 131072)", "fill_steps": filled},
+        "policy_updates_per_sec": ups / elapsed, "updates": ups, "experiences": exps,
+        "mean_recent_episode_reward": float(np.mean(finished[finished != 0])) if np.any(finished != 0) else None,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     # stage timers on a few more steps
     m0 = d.get("meta_phase_ticks").astype(np.float64)
     u0 = d.scalar("policy_update_count")
@@ -1238,15 +1392,7 @@ def run_c5(args):
         top = max(int(r["dispatches"]) for r in rows)
         upd_traffic = sum((float(r["fetch_KB_x2"]) + float(r["write_KB"])) * 1024.0 for r in rows
                           if int(r["dispatches"]) * 2 >= top)
-    out = {
-        "metric": "VRACER experiences/sec, 4096 concurrent CartPole rollouts, 2x256 policy (C5)",
-        "value": exps / elapsed, "unit": "experiences/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "C5: VRACER Normal policy, CartPole env (examples/learning/reinforcement/cartpole, "
-                               "scipy dopri5 restated), 4096 concurrent environments, 2x256 tanh, mini-batch 256, EBPU 1, "
-                               "replay 262144 (start 131072)", "fill_steps": filled},
-        "policy_updates_per_sec": ups / elapsed, "updates": ups, "experiences": exps,
+    out.update({
         "stage_ms": stages,
         "metadata_kernel_phases_us": {"setup_and_importance_weights": meta_us[0], "retrace_chains": meta_us[1],
                                       "loss_gradient_and_metadata": meta_us[2]},
@@ -1270,7 +1416,7 @@ def run_c5(args):
                                   "traffic_source": profile_file("c5_pmc_traffic.csv")[1] if traffic else None,
                                   "algorithmic_flops_per_launch": gemm_flops, "avg_launch_ms": gemm_ms},
         "mean_recent_episode_reward": float(np.mean(finished[finished != 0])) if np.any(finished != 0) else None,
-    }
+    })
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = c5_cpu_baseline()
     print(json.dumps(out), flush=True)

@@ -3,9 +3,9 @@
 # summarised per kernel matching $KPAT by tools/pmc_kernel.py.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp KORALI_AMD_PLAIN_LAUNCH=1
-O=$PWD/gpurun_out/pmcp
+O=$PWD/bench_out/pmcp
 mkdir -p $O
-(cd /tmp && timeout -k 10 200 rocprofv3 --pmc $CTRS --kernel-trace -d $O/run -o run --output-format csv -- python $OLDPWD/bench.py --workload ${WL:-c4} --steps ${STEPS:-2} --warmup 0 --no-cpu-baseline) > $O/log 2>&1
+(cd /tmp && timeout -k 10 200 rocprofv3 --pmc $CTRS --kernel-trace -d $O/run -o run --output-format csv -- python $OLDPWD/bench.py --full --workload ${WL:-c4} --steps ${STEPS:-2} --warmup 0 --no-cpu-baseline) > $O/log 2>&1
 rc=$?
 echo "rc=$rc"
 [ $rc -ne 0 ] && { grep -v "^W20" $O/log | tail -5; exit $rc; }

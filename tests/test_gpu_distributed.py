@@ -36,11 +36,16 @@ def free_port():
 
 
 def launch(tmp_path, ranks, solver, model, transport, cov):
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
-           "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "tools", "distributed_check.py"),
-           str(tmp_path), solver, model, transport, cov]
     env = dict(os.environ, OMP_NUM_THREADS="1", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    for _ in range(3):
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
+               "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "tools", "distributed_check.py"),
+               str(tmp_path), solver, model, transport, cov]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        # the port was free when probed; another process can take it before the
+        # launcher's rendezvous listens (no rank has started then): pick another
+        if r.returncode == 0 or not ("EADDRINUSE" in r.stderr and "next_rendezvous" in r.stderr):
+            break
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return [json.load(open(tmp_path / f"rank{k}.json")) for k in range(ranks)]
 

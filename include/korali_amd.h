@@ -242,6 +242,102 @@ int kg_cmaes_profile_read(kg_cmaes_t h, const char *stage, double *ms_total, siz
  * KORALI_AMD_EXCHANGE_PROFILE=1.  Returns 1 for an end without a begin. */
 int kg_cmaes_profile_mark(kg_cmaes_t h, const char *stage, int phase);
 
+/* ----------------------------------------------------------------- DEA */
+/* Optimizer/DEA (differential evolution), bit-exact to DEA.cpp.base:
+ *
+ *   kg_dea_initialize     DEA::setInitialConfiguration     DEA.cpp.base:15-61
+ *                         (initSamples :87-97)
+ *   kg_dea_prepare        DEA::prepareGeneration           DEA.cpp.base:99-116
+ *                         (mutateSingle :118-176, fixInfeasible :178-190,
+ *                          Optimizer::isSampleFeasible optimizer.cpp.base:5-14,
+ *                          Uniform::getRandomNumber → gsl_rng_uniform)
+ *   kg_dea_eval_builtin   Optimization::evaluate → user objective
+ *                         optimization.cpp.base:26-34, batched over P
+ *   kg_dea_get_candidates / kg_dea_set_fitness
+ *                         KORALI_START/WAITALL/GET of DEA::runGeneration
+ *                         DEA.cpp.base:69-82, :195-196 (host-callback objectives)
+ *   kg_dea_update         DEA::updateSolver                DEA.cpp.base:192-278
+ *   kg_dea_generation     DEA::runGeneration               DEA.cpp.base:63-85
+ *   kg_dea_{get,set}_field / _{get,set}_rng
+ *                         Module::getConfiguration / setConfiguration of the
+ *                         solver state incl. RNG "Range" (distribution.cpp.base:10-62)
+ *
+ * The proposal is a chain over the samples on one workgroup: every draw
+ * comes from one sequential uniform stream and a sample consumes a
+ * data-dependent number of words (the DEA proposal chain).  The
+ * kernel reads a window of `window_words` peeked draws and stops before an
+ * attempt that would run past it; kg_dea_prepare relaunches from there. */
+typedef struct kg_dea_s *kg_dea_t;
+
+enum kg_dea_mutation_rule { KG_DEA_MUTATION_FIXED = 0, KG_DEA_MUTATION_SELF_ADAPTIVE = 1 };
+enum kg_dea_parent_rule { KG_DEA_PARENT_RANDOM = 0, KG_DEA_PARENT_BEST = 1 };
+enum kg_dea_accept_rule {
+  KG_DEA_ACCEPT_BEST = 0,
+  KG_DEA_ACCEPT_GREEDY = 1,
+  KG_DEA_ACCEPT_ITERATIVE = 2,
+  KG_DEA_ACCEPT_IMPROVED = 3
+};
+
+typedef struct {
+  size_t variable_count;     /* N */
+  size_t population_size;    /* P ("Population Size"; >= 4 with parent rule Random, >= 3 with Best) */
+  const double *lower_bound; /* N, finite */
+  const double *upper_bound; /* N, finite, >= lower_bound (DEA.cpp.base:19-21) */
+  double crossover_rate;     /* "Crossover Rate" */
+  double mutation_rate;      /* "Mutation Rate" */
+  int mutation_rule;         /* enum kg_dea_mutation_rule ("Mutation Rule") */
+  int parent_rule;           /* enum kg_dea_parent_rule ("Parent Selection Rule") */
+  int accept_rule;           /* enum kg_dea_accept_rule ("Accept Rule") */
+  int fix_infeasible;        /* "Fix Infeasible" */
+  uint64_t normal_seed;      /* seed of the Normal generator (kept and exported, never drawn from) */
+  uint64_t uniform_seed;     /* seed of the Uniform generator (GSL mt19937) */
+  size_t window_words;       /* uniform draws the proposal kernel sees per launch; 0 → max(4096, 4 P (N + 8)).
+                                A window smaller than one attempt is doubled on demand. */
+  size_t max_windows;        /* windows one kg_dea_prepare may use before it reports a configuration
+                                that cannot become feasible; 0 → 1024.  Not a reference setting: the
+                                reference redraws forever there, and this bound is what turns that into
+                                an error (kg_last_error) instead of a hang. */
+  int device;                /* HIP device ordinal */
+} kg_dea_cfg;
+
+/* Every entry checks its arguments: a null handle or pointer, a stage called
+ * on a handle without a population, or ld < N is an error, not a crash. */
+int kg_dea_create(const kg_dea_cfg *cfg, kg_dea_t *out);
+int kg_dea_destroy(kg_dea_t h);
+int kg_dea_initialize(kg_dea_t h);
+/* candidates of `generation` (generation 1: the initial samples) and
+ * "Previous Value Vector" = "Value Vector" (DEA.cpp.base:115).  Blocks until
+ * the chain is through (one small device read per window). */
+int kg_dea_prepare(kg_dea_t h, size_t generation);
+int kg_dea_eval_builtin(kg_dea_t h, int objective); /* enum kg_objective; "Model Evaluation Count" += P */
+int kg_dea_get_candidates(kg_dea_t h, double *X, size_t ld);
+int kg_dea_set_fitness(kg_dea_t h, const double *F); /* finite values only; "Model Evaluation Count" += P */
+int kg_dea_update(kg_dea_t h, size_t generation);
+/* prepare + eval_builtin + update (generation 1 initializes a fresh handle first) */
+int kg_dea_generation(kg_dea_t h, size_t generation, int objective);
+int kg_dea_synchronize(kg_dea_t h); /* waits and reports device-side errors */
+/* named state fields, keys as in the reference's solver JSON ("Sample
+ * Population", "Candidate Population", "Value Vector", "Previous Value
+ * Vector", "Current Mean", "Previous Mean", "Best Ever Variables", "Current
+ * Best Variables", "Max Distances"; scalars "Best Ever Value", "Previous Best
+ * Ever Value", "Current Best Value", "Previous Best Value", "Best Sample
+ * Index", "Infeasible Sample Count", "Model Evaluation Count", "Mutation
+ * Rate", "Crossover Rate", "Current Minimum Step Size"); sizes in doubles */
+int kg_dea_field_size(kg_dea_t h, const char *name, size_t *n);
+int kg_dea_get_field(kg_dea_t h, const char *name, double *out, size_t n);
+int kg_dea_set_field(kg_dea_t h, const char *name, const double *in, size_t n);
+/* 5000-byte GSL states as for CMA-ES.  which: 0 Normal, 1 Uniform generator. */
+int kg_dea_get_rng(kg_dea_t h, int which, void *state5000);
+int kg_dea_set_rng(kg_dea_t h, int which, const void *state5000);
+/* Diagnostics only (replaces nothing in the reference, holds no solver state):
+ * windows the last kg_dea_prepare used, and the current window size in words.
+ * The tests read it to see that the relaunch and window-growth paths ran. */
+int kg_dea_windows(kg_dea_t h, size_t *last_windows, size_t *window_words);
+/* stage timing as kg_cmaes_profile; stages "words" (stream production and
+ * the uniform conversion), "propose", "evaluate", "update" */
+int kg_dea_profile(kg_dea_t h, int enable);
+int kg_dea_profile_read(kg_dea_t h, const char *stage, double *ms_total, size_t *count);
+
 /* ------------------------------------------------------------ testing */
 /* Host reference of the mt19937 jump-ahead the chunked device producer
  * uses: out = the 624 untempered words `distance` positions after window624

@@ -67,6 +67,21 @@ class _TmcmcCfg(C.Structure):
     ]
 
 
+class _DeaCfg(C.Structure):
+    _fields_ = [
+        ("variable_count", C.c_size_t), ("population_size", C.c_size_t),
+        ("lower_bound", C.POINTER(C.c_double)), ("upper_bound", C.POINTER(C.c_double)),
+        ("crossover_rate", C.c_double), ("mutation_rate", C.c_double), ("mutation_rule", C.c_int),
+        ("parent_rule", C.c_int), ("accept_rule", C.c_int), ("fix_infeasible", C.c_int),
+        ("normal_seed", C.c_uint64), ("uniform_seed", C.c_uint64), ("window_words", C.c_size_t),
+        ("max_windows", C.c_size_t), ("device", C.c_int),
+    ]
+
+
+DEA_MUTATION_RULES = {"fixed": 0, "self adaptive": 1}
+DEA_PARENT_RULES = {"random": 0, "best": 1}
+DEA_ACCEPT_RULES = {"best": 0, "greedy": 1, "iterative": 2, "improved": 3}
+
 EXPORTED = [
     "kg_last_error", "kg_abi_version", "kg_device_count",
     "kg_cmaes_create", "kg_cmaes_destroy", "kg_cmaes_initialize", "kg_cmaes_sample", "kg_cmaes_eval_builtin",
@@ -77,6 +92,10 @@ EXPORTED = [
     "kg_cmaes_get_fields", "kg_cmaes_get_sorting_index", "kg_cmaes_get_rng", "kg_cmaes_set_rng", "kg_cmaes_device_ptr",
     "kg_cmaes_stream", "kg_cmaes_profile", "kg_cmaes_profile_read", "kg_cmaes_profile_mark",
     "kg_cmaes_set_constraints", "kg_cmaes_prepare_constrained", "kg_cmaes_population_size",
+    "kg_dea_create", "kg_dea_destroy", "kg_dea_initialize", "kg_dea_prepare", "kg_dea_eval_builtin",
+    "kg_dea_get_candidates", "kg_dea_set_fitness", "kg_dea_update", "kg_dea_generation", "kg_dea_synchronize",
+    "kg_dea_field_size", "kg_dea_get_field", "kg_dea_set_field", "kg_dea_get_rng", "kg_dea_set_rng",
+    "kg_dea_windows", "kg_dea_profile", "kg_dea_profile_read",
     "kg_tmcmc_create", "kg_tmcmc_destroy", "kg_tmcmc_generation", "kg_tmcmc_synchronize", "kg_tmcmc_field_size",
     "kg_tmcmc_get_field", "kg_tmcmc_set_field", "kg_tmcmc_get_rng", "kg_tmcmc_set_rng", "kg_tmcmc_prepare",
     "kg_tmcmc_evaluate", "kg_tmcmc_process", "kg_tmcmc_advance", "kg_tmcmc_get_pending",
@@ -143,6 +162,23 @@ def lib():
         L.kg_cmaes_profile.argtypes = [vp, ip]
         L.kg_cmaes_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_cmaes_profile_mark.argtypes = [vp, cp, ip]
+        L.kg_dea_create.argtypes = [C.POINTER(_DeaCfg), C.POINTER(vp)]
+        for f in ("kg_dea_destroy", "kg_dea_initialize", "kg_dea_synchronize"):
+            getattr(L, f).argtypes = [vp]
+        for f in ("kg_dea_prepare", "kg_dea_update"):
+            getattr(L, f).argtypes = [vp, sz]
+        L.kg_dea_eval_builtin.argtypes = [vp, ip]
+        L.kg_dea_generation.argtypes = [vp, sz, ip]
+        L.kg_dea_get_candidates.argtypes = [vp, dp, sz]
+        L.kg_dea_set_fitness.argtypes = [vp, dp]
+        L.kg_dea_field_size.argtypes = [vp, cp, C.POINTER(sz)]
+        L.kg_dea_get_field.argtypes = [vp, cp, dp, sz]
+        L.kg_dea_set_field.argtypes = [vp, cp, dp, sz]
+        L.kg_dea_get_rng.argtypes = [vp, ip, vp]
+        L.kg_dea_set_rng.argtypes = [vp, ip, vp]
+        L.kg_dea_windows.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+        L.kg_dea_profile.argtypes = [vp, ip]
+        L.kg_dea_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_tmcmc_create.argtypes = [C.POINTER(_TmcmcCfg), C.POINTER(vp)]
         for f in ("kg_tmcmc_destroy", "kg_tmcmc_synchronize", "kg_tmcmc_evaluate", "kg_tmcmc_evaluate_prior"):
             getattr(L, f).argtypes = [vp]
@@ -412,6 +448,117 @@ class CmaesDevice:
         stage on the handle's stream; returns the C-ABI status (1: an end
         without a begin)."""
         return int(self._L.kg_cmaes_profile_mark(self.h, stage.encode(), int(phase)))
+
+
+class DeaDevice:
+    """One Optimizer/DEA (differential evolution) instance on one MI355X
+    (kg_dea_t), bit-exact to the reference's DEA.cpp.base.  Generator indices
+    for rng_state / set_rng_state: 0 Normal (kept, never drawn from), 1 Uniform."""
+
+    def __init__(self, N, P, lower_bound, upper_bound, crossover_rate=0.9, mutation_rate=0.5, mutation_rule="Fixed",
+                 parent_rule="Random", accept_rule="Greedy", fix_infeasible=True, normal_seed=0, uniform_seed=0,
+                 window_words=0, max_windows=0, device=0):
+        L = lib()
+        self.N, self.P = int(N), int(P)
+        self._arrays = [_vec(lower_bound, self.N, np.nan), _vec(upper_bound, self.N, np.nan)]
+        cfg = _DeaCfg()
+        cfg.variable_count, cfg.population_size = self.N, self.P
+        cfg.lower_bound, cfg.upper_bound = [_dptr(a) for a in self._arrays]
+        cfg.crossover_rate, cfg.mutation_rate = float(crossover_rate), float(mutation_rate)
+        cfg.mutation_rule = DEA_MUTATION_RULES[mutation_rule.lower()] if isinstance(mutation_rule, str) else int(mutation_rule)
+        cfg.parent_rule = DEA_PARENT_RULES[parent_rule.lower()] if isinstance(parent_rule, str) else int(parent_rule)
+        cfg.accept_rule = DEA_ACCEPT_RULES[accept_rule.lower()] if isinstance(accept_rule, str) else int(accept_rule)
+        cfg.fix_infeasible = int(bool(fix_infeasible))
+        cfg.normal_seed, cfg.uniform_seed = int(normal_seed) & (2**64 - 1), int(uniform_seed) & (2**64 - 1)
+        cfg.window_words, cfg.max_windows, cfg.device = int(window_words), int(max_windows), int(device)
+        h = C.c_void_p()
+        check(L.kg_dea_create(C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._L = L
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.kg_dea_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # stages
+    def initialize(self):
+        check(self._L.kg_dea_initialize(self.h))
+
+    def prepare(self, generation):
+        check(self._L.kg_dea_prepare(self.h, int(generation)))
+
+    def evaluate(self, objective):
+        check(self._L.kg_dea_eval_builtin(self.h, OBJECTIVES[objective.lower()] if isinstance(objective, str)
+                                          else int(objective)))
+
+    def update(self, generation):
+        check(self._L.kg_dea_update(self.h, int(generation)))
+
+    def generation(self, generation, objective):
+        obj = OBJECTIVES[objective.lower()] if isinstance(objective, str) else int(objective)
+        check(self._L.kg_dea_generation(self.h, int(generation), obj))
+
+    def synchronize(self):
+        check(self._L.kg_dea_synchronize(self.h))
+
+    # host-callback objectives
+    def candidates(self):
+        X = np.empty((self.P, self.N))
+        check(self._L.kg_dea_get_candidates(self.h, _dptr(X), self.N))
+        return X
+
+    def set_fitness(self, F):
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.shape != (self.P,):
+            raise ValueError("fitness vector has shape %s, expected (%d,)" % (F.shape, self.P))
+        check(self._L.kg_dea_set_fitness(self.h, _dptr(F)))
+
+    # state
+    def field_size(self, name):
+        n = C.c_size_t()
+        check(self._L.kg_dea_field_size(self.h, name.encode(), C.byref(n)))
+        return n.value
+
+    def __getitem__(self, name):
+        n = self.field_size(name)
+        out = np.empty(n)
+        check(self._L.kg_dea_get_field(self.h, name.encode(), _dptr(out), n))
+        return out
+
+    def __setitem__(self, name, value):
+        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
+        check(self._L.kg_dea_set_field(self.h, name.encode(), _dptr(a), a.size))
+
+    def rng_state(self, which=1):
+        buf = C.create_string_buffer(5000)
+        check(self._L.kg_dea_get_rng(self.h, int(which), buf))
+        return buf.raw
+
+    def set_rng_state(self, state, which=1):
+        assert len(state) == 5000
+        buf = C.create_string_buffer(bytes(state), 5000)
+        check(self._L.kg_dea_set_rng(self.h, int(which), buf))
+
+    def windows(self):
+        """(windows the last prepare() used, current window size in words)"""
+        a, b = C.c_size_t(), C.c_size_t()
+        check(self._L.kg_dea_windows(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def profile(self, enable=True):
+        check(self._L.kg_dea_profile(self.h, int(enable)))
+
+    def profile_read(self, stage):
+        ms, n = C.c_double(), C.c_size_t()
+        check(self._L.kg_dea_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
 
 class TmcmcDevice:

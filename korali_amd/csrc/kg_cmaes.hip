@@ -1287,6 +1287,138 @@ __global__ void __launch_bounds__(256) k_select_prep(int N, int mu, unsigned lon
   }
 }
 
+// k_rank_sort + k_select_prep in one launch (the plain exact update,
+// 256 < lambda <= RANK_MAX).  Workgroup b ranks keys 16 b .. 16 b + 15 as
+// k_rank_sort does (descending F, ties by index, -0.0 == +0.0 as the FP
+// compare has it) and writes idx[r] = i; a sample with r < mu is then
+// scattered straight to row r of Y / Yc / T by the workgroup that ranked it,
+// so the grid-wide order between the two kernels is not needed.  The loads of
+// the 16 population rows (16 threads per row, columns c, c + 16, ...: the
+// first 128 columns in registers) are issued before the compare loop.  The
+// workgroup holding rank 0 does the best bookkeeping; workgroup 0 copies m
+// into m_prev.  k_select_prep's rules hold unchanged: the factors take m
+// (equal to m_prev until the mean kernel writes it), and the out-of-range
+// flag is cleared by the previous update's k_sigma, never inside this launch.
+constexpr int RS_U = 8;  // register-held columns per thread (16 RS_U = 128)
+__global__ void __launch_bounds__(256) k_rank_select(int lam, int N, int mu, unsigned long long gen,
+                                                     const double *__restrict__ F, unsigned *__restrict__ out,
+                                                     const double *__restrict__ X, const double *__restrict__ w,
+                                                     const double *__restrict__ mean, double *__restrict__ prevMean,
+                                                     double *__restrict__ Y, double *__restrict__ currBestVars,
+                                                     double *__restrict__ bestEverVars, CmaesScalars *sc,
+                                                     double *__restrict__ Yc, double *__restrict__ Tt) {
+  extern __shared__ __attribute__((aligned(16))) double rk[];
+  __shared__ unsigned part[16][17];
+  __shared__ unsigned rank_s[16];
+  __shared__ int flag;
+  // this thread's share of the row work: sample 16 b + row, columns c + 16 u
+  const int row = threadIdx.x >> 4, c = threadIdx.x & 15;
+  const int is = blockIdx.x * 16 + row;
+  double xv[RS_U], mv[RS_U];
+#pragma unroll
+  for (int u = 0; u < RS_U; u++) {
+    const int d = c + 16 * u;
+    xv[u] = (is < lam && d < N) ? X[(size_t)is * N + d] : 0.0;
+    mv[u] = d < N ? mean[d] : 0.0;
+  }
+  const double effMu = sc->effectiveMu, ca = N + 1.3, cb = N + 2.0;
+  const double ccov1 = 2.0 / (ca * ca + effMu);
+  double ccovmu = 2.0 * (effMu - 2. + 1. / effMu) / (cb * cb + effMu);
+  if (1.0 - ccov1 < ccovmu) ccovmu = 1.0 - ccov1;
+  for (int q0 = threadIdx.x; q0 < lam; q0 += 8 * blockDim.x) {  // eight loads in flight per thread
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) v[u] = (q0 + u * (int)blockDim.x < lam) ? F[q0 + u * blockDim.x] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; u++)
+      if (q0 + u * (int)blockDim.x < lam) rk[q0 + u * blockDim.x] = v[u];
+  }
+  if (blockIdx.x == 0)
+    for (int d = threadIdx.x; d < N; d += blockDim.x) prevMean[d] = mean[d];
+  __syncthreads();
+  {
+    // k_rank_sort's compare loop: thread group p scans one sixteenth of the keys
+    const int li = threadIdx.x & 15, p = threadIdx.x >> 4;
+    const int i = blockIdx.x * 16 + li;
+    const double ki = (i < lam) ? rk[i] : 0.0;
+    const int per = (lam + 15) / 16, j0 = p * per, j1 = min(lam, j0 + per);
+    unsigned cnt = 0;
+    int j = j0;
+    for (; j + 8 <= j1; j += 8) {
+      double kj[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) kj[u] = rk[j + u];
+#pragma unroll
+      for (int u = 0; u < 8; u++) cnt += (kj[u] > ki || (kj[u] == ki && j + u < i)) ? 1u : 0u;
+    }
+    for (; j < j1; j++) {
+      const double kj = rk[j];
+      cnt += (kj > ki || (kj == ki && j < i)) ? 1u : 0u;
+    }
+    part[p][li] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    unsigned r = 0;
+    for (int q = 0; q < 16; q++) r += part[q][threadIdx.x];
+    rank_s[threadIdx.x] = r;
+    if (blockIdx.x * 16 + (int)threadIdx.x < lam) out[r] = (unsigned)(blockIdx.x * 16 + threadIdx.x);
+  }
+  __syncthreads();
+  const unsigned r = rank_s[row];
+  const bool sel = is < lam && r < (unsigned)mu;
+  bool ok = true;
+  if (sel) {
+    const double cw = ccovmu * w[r];
+    auto put = [&](int d, double x, double m) {
+      Y[(size_t)r * N + d] = x;
+      const double yc = x - m;
+      Yc[(size_t)r * N + d] = yc;
+      const double t = cw * yc;
+      Tt[(size_t)d * mu + r] = t;
+      ok = ok && rmu_in_range(yc) && rmu_in_range(t);
+    };
+#pragma unroll
+    for (int u = 0; u < RS_U; u++)
+      if (c + 16 * u < N) put(c + 16 * u, xv[u], mv[u]);
+    for (int d = c + 16 * RS_U; d < N; d += 16) put(d, X[(size_t)is * N + d], mean[d]);
+  }
+  if (__syncthreads_or(!ok) && threadIdx.x == 0) atomicOr(&sc->rmuOutOfRange, 1u);
+  // updateDistribution's best bookkeeping (:547-560), as k_update_best, in
+  // the workgroup (and the 16 threads) holding the best sample
+  const bool best = is < lam && r == 0u;
+  if (!__syncthreads_or(best)) return;
+  if (best && c == 0) {
+    sc->bestValidSample = (double)is;
+    sc->previousBestValue = sc->currentBestValue;
+    sc->currentBestValue = rk[is];
+    const int fl = (sc->currentBestValue > sc->bestEverValue || gen == 1) ? 1 : 0;
+    flag = fl;
+    sc->bestFlag = (unsigned)fl;
+    if (fl) {
+      sc->previousBestEverValue = sc->bestEverValue;
+      sc->bestEverValue = sc->currentBestValue;
+    }
+  }
+  __syncthreads();
+  if (best) {
+    const int fl = flag;
+#pragma unroll
+    for (int u = 0; u < RS_U; u++) {
+      const int d = c + 16 * u;
+      if (d < N) {
+        currBestVars[d] = xv[u];
+        if (fl) bestEverVars[d] = xv[u];
+      }
+    }
+    for (int d = c + 16 * RS_U; d < N; d += 16) {
+      const double v = X[(size_t)is * N + d];
+      currBestVars[d] = v;
+      if (fl) bestEverVars[d] = v;
+    }
+  }
+}
+
 // one wave per row d (4 rows per workgroup), one lane per column e (64
 // columns per workgroup).  Per chunk of AX_K k: the workgroup stages the
 // Yc rows of its 64 columns and the T values of its 4 rows in LDS (the next
@@ -1669,6 +1801,10 @@ __device__ __forceinline__ double ar_run(double acc, int N, int mu, int d0, int 
 // lower-triangle results go to pack[d (d + 1) / 2 + e] (the sharded
 // exchange buffer, "Shard Covariance") instead of C, entries that adaptC
 // leaves unchanged (diagonal covariance) with their old value
+// (The kernel does not hand C to the host itself: with k_publish_c's
+// protocol inside it -- a system-scope fence per thread, one counter add per
+// tile -- its 528 workgroups took 70 us at C2 against 30.6 + 7.9 us for the
+// two launches)
 __global__ void __launch_bounds__(AR_NT) k_adaptC_row(int N, int mu, int diagonal, const double *__restrict__ Yc,
                                                     const double *__restrict__ Tt, const double *__restrict__ pc,
                                                     double *C, const CmaesScalars *__restrict__ sc, int tbase,
@@ -1988,11 +2124,48 @@ __global__ void __launch_bounds__(256) k_mean2(int N, int mu, const double *__re
 // chunk's loads in flight while the current one is summed.
 // (MR_K = 256: one chunk's sum, 256 x ~9 cycles, covers the next chunk's
 // load latency, which 128-term chunks did not: 20 us at C2)
+//
+// k_mean3<true> is the mean and the evolution paths in one launch (the plain
+// exact update, N <= 128, no gradient step): workgroups 0 .. ceil(N/16)-1 are
+// the mean workgroups (threads 0..255 of each; the rest leave at once), and
+// one more workgroup, the highest block index, is k_paths3.  It loads
+// everything k_paths3 loads except the mean update, then waits for the mean
+// workgroups, so B's column walks and the scalars no longer start cold after
+// the mean.  Hand-off: every thread that stored a mean / meanUpdate entry
+// executes an agent-scope release fence, its workgroup meets at a barrier and
+// one thread adds 1 to `arrived` (device scope, relaxed); one lane of the
+// paths workgroup polls `arrived` (relaxed, s_sleep, bounded by KG_SPIN_LIMIT
+// -> KG_ERR_SYNC_TIMEOUT) until it reaches `target`, executes one agent-scope
+// acquire fence, and after the workgroup barrier the mean update is read by
+// vector loads through a pointer that is not const __restrict__.  `arrived`
+// starts at zero (kg_cmaes_create's zero fill of the allocation, waited for
+// there) and is never reset afterwards: launches on the stream are ordered
+// and every mean workgroup adds exactly once, so the host's running total
+// (target, compared modulo 2^32) tags the launch.  A plain launch: the mean
+// workgroups have the lower indices, are dispatched first and wait on
+// nothing.  The mean workgroups' waves 4..15 end before the barriers: a wave
+// that has ended is not counted at s_barrier, which is a property of this
+// hardware and not a guarantee of the language.  The instance is compiled
+// for 1024-thread workgroups, so the mean part is limited to 128 VGPRs.
 constexpr int MR_K = 256, MR_KS = MR_K + 2, MR_U = MR_K * 16 / 256;
-__global__ void __launch_bounds__(256) k_mean3(int N, int mu, const double *__restrict__ Y,
-                                               const double *__restrict__ w, double *mean,
-                                               const double *__restrict__ prevMean, double *meanUpdate,
-                                               const CmaesScalars *__restrict__ sc) {
+constexpr int PR_T = 1024;
+template <bool kWait>
+__device__ void paths3_body(int N, unsigned long long gen, const double *__restrict__ B, const double *__restrict__ D,
+                            const double *meanUpdate, double *auxBDZ, double *ps, double *pc, CmaesScalars *sc,
+                            unsigned *arrived, unsigned target);
+template <bool kPaths>
+__global__ void __launch_bounds__(kPaths ? PR_T : 256)
+    k_mean3(int N, int mu, const double *__restrict__ Y, const double *__restrict__ w, double *mean,
+            const double *__restrict__ prevMean, double *meanUpdate, CmaesScalars *sc, unsigned long long gen,
+            const double *__restrict__ B, const double *__restrict__ D, double *auxBDZ, double *ps, double *pc,
+            unsigned *arrived, unsigned target) {
+  if (kPaths) {
+    if (blockIdx.x == gridDim.x - 1) {
+      paths3_body<true>(N, gen, B, D, meanUpdate, auxBDZ, ps, pc, sc, arrived, target);
+      return;
+    }
+    if (threadIdx.x >= 256) return;  // (gfx9 s_barrier does not count ended waves; see above)
+  }
   __shared__ double ys[2][16][MR_KS];
   __shared__ double ws[2][MR_K];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -2042,6 +2215,11 @@ __global__ void __launch_bounds__(256) k_mean3(int N, int mu, const double *__re
   if (j == 0 && d < N) {
     mean[d] = acc;
     meanUpdate[d] = (acc - pmd) / sig;  // (prevMean: copied by k_gather_selected / k_select_prep)
+    if (kPaths) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this thread's entries before the count
+  }
+  if (kPaths) {
+    __syncthreads();
+    if (tid == 0) __hip_atomic_fetch_add(arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -2050,10 +2228,13 @@ __global__ void __launch_bounds__(256) k_mean3(int N, int mu, const double *__re
 // N = 128).  Every B value the two layers read is loaded at the start
 // (layer 1: columns of B, layer 2: rows), so the only waits between them
 // are the workgroup barriers.
-constexpr int PR_T = 1024;
-__global__ void __launch_bounds__(PR_T) k_paths3(int N, unsigned long long gen, const double *__restrict__ B,
-                                                 const double *__restrict__ D, const double *__restrict__ meanUpdate,
-                                                 double *auxBDZ, double *ps, double *pc, CmaesScalars *sc) {
+// kWait (k_mean3<true>'s last workgroup): the mean update is read only after
+// the mean workgroups have arrived, everything else before.
+template <bool kWait>
+__device__ __forceinline__ void paths3_body(int N, unsigned long long gen, const double *__restrict__ B,
+                                            const double *__restrict__ D, const double *meanUpdate, double *auxBDZ,
+                                            double *ps, double *pc, CmaesScalars *sc, unsigned *arrived,
+                                            unsigned target) {
   __shared__ double mu_s[128 + 16], aux_s[128 + 16], pn_s[128 + 16];
   __shared__ int hs;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -2061,7 +2242,8 @@ __global__ void __launch_bounds__(PR_T) k_paths3(int N, unsigned long long gen, 
   const double cs = sc->sigmaCumulationFactor, effMu = sc->effectiveMu, cc = sc->cumulativeCovariance;
   // every other operand read up front with B (one round of loads, not one per phase)
   const double chi = sc->chiSquareNumber, hpGen = sc->hsigPowGen, hpCs = sc->hsigPowCs, hp = sc->hsigPow;
-  const double pcq = tid < N ? pc[tid] : 0.0, muq = tid < N ? meanUpdate[tid] : 0.0;
+  const double pcq = tid < N ? pc[tid] : 0.0;
+  double muq = (!kWait && tid < N) ? meanUpdate[tid] : 0.0;
   double Dd[2], psd[2];
 #pragma unroll
   for (int p = 0; p < 2; p++) {
@@ -2082,6 +2264,27 @@ __global__ void __launch_bounds__(PR_T) k_paths3(int N, unsigned long long gen, 
       b1[p][g] = ok ? B[(size_t)e * N + d] : 0.0;  // B[e][d]: aux = D^-1 B^T mu   (:627-636)
       b2[p][g] = ok ? B[(size_t)d * N + e] : 0.0;  // B[d][e]: B aux               (:641-651)
     }
+  }
+  if (kWait) {
+    __shared__ int arrivedOk;
+    if (tid == 0) {
+      int ok = 1;
+      for (unsigned spins = 0;; spins++) {
+        const unsigned a = __hip_atomic_load(arrived, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((int)(a - target) >= 0) break;
+        if (spins > KG_SPIN_LIMIT) {
+          atomicOr(&sc->errors, KG_ERR_SYNC_TIMEOUT);
+          ok = 0;
+          break;
+        }
+        __builtin_amdgcn_s_sleep(2);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      arrivedOk = ok;
+    }
+    __syncthreads();
+    if (!arrivedOk) return;
+    muq = tid < N ? meanUpdate[tid] : 0.0;
   }
   for (int q = tid; q < 128 + 16; q += PR_T) {
     mu_s[q] = q < N ? meanUpdate[q] : 0.0;
@@ -2143,6 +2346,11 @@ __global__ void __launch_bounds__(PR_T) k_paths3(int N, unsigned long long gen, 
   __syncthreads();
   const double fac2 = sqrt(cc * (2. - cc) * effMu);
   if (tid < N) pc[tid] = (1. - cc) * pcq + hs * fac2 * muq;  // (N <= 128 < PR_T)
+}
+__global__ void __launch_bounds__(PR_T) k_paths3(int N, unsigned long long gen, const double *__restrict__ B,
+                                                 const double *__restrict__ D, const double *__restrict__ meanUpdate,
+                                                 double *auxBDZ, double *ps, double *pc, CmaesScalars *sc) {
+  paths3_body<false>(N, gen, B, D, meanUpdate, auxBDZ, ps, pc, sc, nullptr, 0u);
 }
 
 // evolution paths for N <= 128 (full covariance): B staged once in LDS (row
@@ -3003,6 +3211,14 @@ struct kg_cmaes_s {
   TermSummary *summary = nullptr, *summaryDev = nullptr;
   unsigned long long updates = 0;
   bool sampleBegun = false;  // kg_cmaes_begin_sample enqueued the next draw's first half
+  // the draw's k_consume is not enqueued yet (flush_consume): it leaves the
+  // update's critical path and runs after C's hand-off to the host
+  bool consumePending = false;
+  // KORALI_AMD_FUSED_SELECT=0 / KORALI_AMD_EARLY_PUBLISH=0 (A/B, read when the
+  // handle is created): the separate selection kernels / publish after sigma
+  bool fusedSel = true, earlyPub = true;
+  unsigned *meanArrived = nullptr;  // k_mean3<true>'s arrival counter (zero from create's fill, then monotonic)
+  unsigned meanTarget = 0;          // its value once the launch enqueued last has arrived
   MtStream normal, uniform;
   // profiling
   bool profile = false;
@@ -3032,6 +3248,19 @@ struct Stage {
     }
   }
 };
+
+// The plain draw's consume (one thread advancing the Normal stream's state)
+// is deferred by kg_cmaes_sample: nothing between the draw and C's hand-off
+// to the host reads that state, so kg_cmaes_update enqueues it after the
+// hand-off.  Every entry point that reads or writes generator state, starts a
+// draw, collects the error flags, synchronises or destroys the handle calls
+// this first, so the state seen through the API never lags.
+int flush_consume(kg_cmaes_s *h) {
+  if (!h->consumePending) return 0;
+  h->consumePending = false;
+  Stage st(h, "rng_consume");
+  return h->normal.consume_normals_dev(h->usedBlocks, h->N, h->blockEnd, h->stream);
+}
 
 // eigensolver stage profiling: device stages by events, host stages by clock
 void eig_prof(void *ctx, const char *stage, int phase) {
@@ -3108,6 +3337,7 @@ __global__ void k_collect_errors(CmaesScalars *sc, const StreamState *a, const S
 int check_errors(kg_cmaes_s *h) {
   // one read: the generators' flags are folded into the scalar block first
   unsigned int e = 0;
+  if (flush_consume(h)) return 1;
   hipLaunchKernelGGL(k_collect_errors, dim3(1), dim3(1), 0, h->stream, h->sc, h->normal.state(), h->uniform.state());
   KG_HIP(hipGetLastError());
   KG_HIP(hipMemcpyAsync(&e, &h->sc->errors, sizeof(e), hipMemcpyDeviceToHost, h->stream));
@@ -3343,7 +3573,7 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
   if (cfg->cov_mode != KG_COV_MFMA) rc |= dalloc_q(&h->Yc, (size_t)h->muMax * N) | dalloc_q(&h->Tt, (size_t)h->muMax * N);
   rc |= dalloc_q(&h->idx, L) | dalloc_q(&h->sc, 1);
   rc |= dalloc_q(&h->infeas, xrows) | dalloc_q(&h->assign, L) | dalloc_q(&h->blockEnd, rows) | dalloc_q(&h->usedBlocks, 1);
-  rc |= dalloc_q(&h->selEnd, 2);
+  rc |= dalloc_q(&h->selEnd, 2) | dalloc_q(&h->meanArrived, 1);
   if (h->cfg.store_bdz) rc |= dalloc_q(&h->BDZ, (size_t)L * N);
   if (cfg->use_gradients) rc |= dalloc_q(&h->G, (size_t)L * N);
   rc |= dalloc_q(&h->gran, N) | dalloc_q(&h->mask, N) | dalloc_q(&h->maskSigma, N);
@@ -3398,7 +3628,10 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
   }
   memset(h->summary, 0, sizeof(TermSummary));
   if (L <= RANK_MAX && (size_t)L * sizeof(double) > 64 * 1024)
+  {
     KG_HIP(allow_dynamic_lds((const void *)k_rank_sort, (int)((size_t)L * sizeof(double))));
+    KG_HIP(allow_dynamic_lds((const void *)k_rank_select, (int)((size_t)L * sizeof(double))));
+  }
   {
     const size_t pbytes = ((size_t)N * (PA_EC + 1) + N) * sizeof(double);
     if (pbytes > 64 * 1024)
@@ -3428,6 +3661,12 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
     }
   }
   clk.mark("eigen");
+  {
+    const char *e = getenv("KORALI_AMD_FUSED_SELECT");
+    h->fusedSel = !(e && *e == '0');
+    e = getenv("KORALI_AMD_EARLY_PUBLISH");
+    h->earlyPub = !(e && *e == '0');
+  }
   if (set_current(h, h->lamCfg, h->muCfg)) return 1;
   KG_HIP(hipMemcpy(h->lb, lb.data(), N * sizeof(double), hipMemcpyHostToDevice));
   KG_HIP(hipMemcpy(h->ub, ub.data(), N * sizeof(double), hipMemcpyHostToDevice));
@@ -3457,6 +3696,7 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
 int kg_cmaes_destroy(kg_cmaes_t h) {
   if (!h) return 0;
   // every stream drained before the blocks go back to the cache
+  (void)flush_consume(h);
   (void)hipStreamSynchronize(h->stream);
   if (h->stream2) (void)hipStreamSynchronize(h->stream2);
   h->eig.drain();
@@ -3474,7 +3714,7 @@ int kg_cmaes_destroy(kg_cmaes_t h) {
                   (void *)h->gran, (void *)h->mask, (void *)h->maskSigma, (void *)h->ubuf, (void *)h->uused,
                   (void *)h->selEnd, (void *)h->V, (void *)h->auxC, (void *)h->violDev, (void *)h->pairI,
                   (void *)h->pairC, (void *)h->pairCnt, (void *)h->listDev, (void *)h->dzT, (void *)h->shardPos,
-                  (void *)h->shardCounts, (void *)h->rows, (void *)h->covPack})
+                  (void *)h->shardCounts, (void *)h->rows, (void *)h->covPack, (void *)h->meanArrived})
     if (p) dev_release(p);
   for (auto &t : h->pending) {
     (void)hipEventDestroy(std::get<1>(t));
@@ -3540,6 +3780,7 @@ static int cmaes_draw_begin(kg_cmaes_t h) {
 int kg_cmaes_begin_sample(kg_cmaes_t h) {
   if (h->sampleBegun) return 0;
   if (h->nc) return 0;  // CCMA-ES: the regime check may reset C before the next draw
+  if (flush_consume(h)) return 1;  // (the draw starts from the advanced state)
   if (cmaes_draw_begin(h)) return 1;
   h->eig.trace = h->eigTrace;
   if (h->eig.run_begin(h->C, h->cfg.diagonal_covariance, h->B, h->D, &h->sc->minEig, &h->sc->maxEig,
@@ -3721,8 +3962,11 @@ static int cmaes_resample(kg_cmaes_t h) {
   return 0;
 }
 
+static bool plain_update(kg_cmaes_t h);  // (with kg_cmaes_update)
+
 int kg_cmaes_sample(kg_cmaes_t h) {
   const int N = h->N;
+  if (flush_consume(h)) return 1;  // (a draw whose update never came)
   if (!h->sampleBegun && cmaes_draw_begin(h)) return 1;
   h->sampleBegun = false;
   if (cmaes_eigen(h)) return 1;
@@ -3755,10 +3999,11 @@ int kg_cmaes_sample(kg_cmaes_t h) {
     // for 32 x 128 / 64 x 64 against 1.73 ms)
     if (cmaes_transform(h, trows, xo, bo, 1, h->mirrored ? 1 : 0)) return 1;
   }
-  {
-    Stage st(h, "rng_consume");
-    if (h->normal.consume_normals_dev(h->usedBlocks, N, h->blockEnd, h->stream)) return 1;
-  }
+  // ahead of a plain exact update the draw leaves its consume to flush_consume
+  // (after the update's hand-off of C, or the first entry point that needs
+  // the state); every other configuration consumes here, as before
+  h->consumePending = true;
+  if (!plain_update(h)) return flush_consume(h);
   return 0;
 }
 
@@ -3874,6 +4119,12 @@ static bool row_chains() {
     return !(e && *e == '0');
   }();
   return on;
+}
+
+static void launch_mean3(kg_cmaes_t h) {
+  hipLaunchKernelGGL(k_mean3<false>, dim3((h->N + 15) / 16), dim3(256), 0, h->stream, h->N, h->mu, h->Y, h->w, h->mean,
+                     h->prevMean, h->meanUpdate, h->sc, 0ULL, (const double *)nullptr, (const double *)nullptr,
+                     (double *)nullptr, (double *)nullptr, (double *)nullptr, (unsigned *)nullptr, 0u);
 }
 
 static int cmaes_paths(kg_cmaes_t h, size_t generation) {
@@ -4099,41 +4350,64 @@ static int ccm_after_update(kg_cmaes_t h) {
 // k_sigma, so the host starts on C while sigma and the record are computed.
 // (CCMA-ES may still reset C in ccm_after_update; KORALI_AMD_EARLY_PUBLISH=0
 // restores the order publish-after-sigma.)
+static bool early_publish_on(kg_cmaes_t h) {
+  return h->earlyPub && !h->nc && h->eig.host_tridiag() && !h->cfg.diagonal_covariance;
+}
 static int early_publish(kg_cmaes_t h) {
-  static const bool early = [] {
-    const char *e = getenv("KORALI_AMD_EARLY_PUBLISH");
-    return !(e && *e == '0');
-  }();
-  if (!early || h->nc || !h->eig.host_tridiag() || h->cfg.diagonal_covariance) return 0;
+  if (!early_publish_on(h)) return 0;
   h->eig.trace = h->eigTrace;
   return h->eig.run_begin(h->C, 0, h->B, h->D, &h->sc->minEig, &h->sc->maxEig, &h->sc->eigenFailures, &h->sc->errors,
                           h->stream, eig_prof, h);
 }
 
+static bool fused_select(kg_cmaes_t h) {
+  const bool ccm = h->nc > 0 && !h->viability;
+  return h->fusedSel && !ccm && h->nc == 0 && h->cfg.mu_type != KG_MU_PROPORTIONAL &&
+         h->cfg.cov_mode != KG_COV_MFMA && h->updates > 0;
+}
+// the plain exact path (the default of kg_cmaes_generation and the engine) of
+// the update that follows: fused_select, additionally one shard, the full
+// covariance handed to the host tridiagonalisation right after adaptC, and
+// lambda in k_rank_sort's range.  (h->updates changes only in k_sigma's
+// launch, so kg_cmaes_sample and the kg_cmaes_update after it agree.)
+static bool plain_update(kg_cmaes_t h) {
+  return h->shards == 1 && fused_select(h) && early_publish_on(h) && row_chains() && h->lam > 256 &&
+         h->lam <= RANK_MAX;
+}
+
 int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
   KG_CHECK(h->shards == 1, "a population-sharded handle updates through kg_cmaes_update_partial / _finalize");
   const int N = h->N, mu = h->mu;
-  if (cmaes_sort(h)) return 1;
+  const bool ccm = h->nc > 0 && !h->viability;  // the best VALID sample (:551-558)
+  // one launch for the best bookkeeping, the gather and the exact factors
+  // when nothing between them needs a grid-wide order (no constraints, no
+  // proportional weights, a k_sigma already cleared the range flag;
+  // KORALI_AMD_FUSED_SELECT=0: the three kernels)
+  const bool fused = fused_select(h);
+  // the plain exact path: its tail runs in fused launches (k_rank_select;
+  // k_mean3<true>, the mean with the paths); every other configuration keeps
+  // the separate kernels.
+  const bool plain = plain_update(h);
+  if (plain) {
+    Stage st(h, "sort");  // the ranking with the selection's scatter (k_rank_select)
+    hipLaunchKernelGGL(k_rank_select, dim3((h->lam + 15) / 16), dim3(256), (size_t)h->lam * sizeof(double), h->stream,
+                       h->lam, N, mu, (unsigned long long)generation, h->F, h->idx, h->X, h->w, h->mean, h->prevMean,
+                       h->Y, h->currBestVars, h->bestEverVars, h->sc, h->Yc, h->Tt);
+    KG_HIP(hipGetLastError());
+  } else if (cmaes_sort(h)) {
+    return 1;
+  }
   {
     Stage st(h, "mean_paths");
-    const bool ccm = h->nc > 0 && !h->viability;  // the best VALID sample (:551-558)
     if (ccm) {
       std::vector<int> viol(h->lam);
       for (int i = 0; i < h->lam; i++) viol[i] = h->cCnt[i] > 0 ? 1 : 0;
       KG_HIP(hipMemcpyAsync(h->violDev, viol.data(), h->lam * sizeof(int), hipMemcpyHostToDevice, h->stream));
       KG_HIP(hipStreamSynchronize(h->stream));  // (viol is a temporary)
     }
-    // one launch for the best bookkeeping, the gather and the exact factors
-    // when nothing between them needs a grid-wide order (no constraints, no
-    // proportional weights, a k_sigma already cleared the range flag;
-    // KORALI_AMD_FUSED_SELECT=0: the three kernels)
-    static const bool fusedSel = [] {
-      const char *e = getenv("KORALI_AMD_FUSED_SELECT");
-      return !(e && *e == '0');
-    }();
-    const bool fused = fusedSel && !ccm && h->nc == 0 && h->cfg.mu_type != KG_MU_PROPORTIONAL &&
-                       h->cfg.cov_mode != KG_COV_MFMA && h->updates > 0;
-    if (fused) {
+    if (plain) {
+      // (k_rank_select did the selection)
+    } else if (fused) {
       hipLaunchKernelGGL(k_select_prep, dim3((mu + RP_T - 1) / RP_T, (N + RP_T - 1) / RP_T), dim3(256), 0, h->stream,
                          N, mu, (unsigned long long)generation, h->X, h->F, h->idx, h->w, h->mean, h->prevMean, h->Y,
                          h->currBestVars, h->bestEverVars, h->sc, h->Yc, h->Tt);
@@ -4163,16 +4437,27 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
                          h->stream, N, mu, h->Y, h->w, h->prevMean, h->sc, h->Yc, h->Tt);
       KG_HIP(hipGetLastError());
     }
-    if (row_chains())
-      hipLaunchKernelGGL(k_mean3, dim3((N + 15) / 16), dim3(256), 0, h->stream, N, mu, h->Y, h->w, h->mean,
-                         h->prevMean, h->meanUpdate, h->sc);
-    else
-      hipLaunchKernelGGL(k_mean2, dim3((N + MN_D - 1) / MN_D), dim3(256), mean2_lds_bytes(), h->stream, N, mu,
-                         h->Y, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
-    if (h->G)
-      hipLaunchKernelGGL(k_mean_gradient, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, mu, h->cfg.gradient_step_size,
-                         h->G, h->idx, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
-    if (cmaes_paths(h, generation)) return 1;
+    if (plain && N <= 128 && !h->G) {
+      // the mean and the evolution paths in one launch (k_mean3<true>)
+      const int nMean = (N + 15) / 16;
+      unsigned target = h->meanTarget + (unsigned)nMean;
+      int n = N, m = mu;
+      unsigned long long gen = (unsigned long long)generation;
+      void *args[] = {&n,   &m,    &h->Y, &h->w,      &h->mean, &h->prevMean, &h->meanUpdate,  &h->sc,
+                      &gen, &h->B, &h->D, &h->auxBDZ, &h->ps,   &h->pc,       &h->meanArrived, &target};
+      KG_HIP(launch_resident((const void *)k_mean3<true>, dim3(nMean + 1), dim3(PR_T), args, 0, h->stream, true));
+      h->meanTarget = target;  // (only a launch that was made adds to the counter)
+    } else {
+      if (row_chains())
+        launch_mean3(h);
+      else
+        hipLaunchKernelGGL(k_mean2, dim3((N + MN_D - 1) / MN_D), dim3(256), mean2_lds_bytes(), h->stream, N, mu,
+                           h->Y, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
+      if (h->G)
+        hipLaunchKernelGGL(k_mean_gradient, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, mu,
+                           h->cfg.gradient_step_size, h->G, h->idx, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
+      if (cmaes_paths(h, generation)) return 1;
+    }
   }
   {
     Stage st(h, "covariance");
@@ -4201,6 +4486,7 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
     KG_HIP(hipGetLastError());
   }
   if (early_publish(h)) return 1;
+  if (flush_consume(h)) return 1;  // the draw's consume: behind C's hand-off, ahead of k_sigma's record
   if (cmaes_sigma(h, generation)) return 1;  // (k_sigma also publishes the termination record)
   return h->nc ? ccm_after_update(h) : 0;
 }
@@ -4279,8 +4565,7 @@ int kg_cmaes_update_rows(kg_cmaes_t h, size_t generation) {
     hipLaunchKernelGGL(k_rankmu_prep, dim3((mu + RP_T - 1) / RP_T, (N + RP_T - 1) / RP_T), dim3(256), 0, h->stream, N,
                        mu, h->Y, h->w, h->prevMean, h->sc, h->Yc, h->Tt);
     if (row_chains())
-      hipLaunchKernelGGL(k_mean3, dim3((N + 15) / 16), dim3(256), 0, h->stream, N, mu, h->Y, h->w, h->mean,
-                         h->prevMean, h->meanUpdate, h->sc);
+      launch_mean3(h);
     else
       hipLaunchKernelGGL(k_mean2, dim3((N + MN_D - 1) / MN_D), dim3(256), mean2_lds_bytes(), h->stream, N, mu, h->Y,
                          h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
@@ -4319,6 +4604,7 @@ int kg_cmaes_update_finalize(kg_cmaes_t h, size_t generation) {
     hipLaunchKernelGGL(k_shard_cov_unpack, dim3(N), dim3(256), 0, h->stream, N, (const double *)h->covPack, h->C);
     KG_HIP(hipGetLastError());
     if (early_publish(h)) return 1;
+    if (flush_consume(h)) return 1;  // (a one-shard handle driven through the staged update)
     return cmaes_sigma(h, generation);
   }
   {
@@ -4338,6 +4624,7 @@ int kg_cmaes_update_finalize(kg_cmaes_t h, size_t generation) {
                        h->cfg.diagonal_covariance, h->part + 2 * (size_t)N, h->pc, h->C, h->sc, 1);
     KG_HIP(hipGetLastError());
   }
+  if (flush_consume(h)) return 1;
   return cmaes_sigma(h, generation);  // (k_sigma also publishes the termination record, as after kg_cmaes_update)
 }
 
@@ -4373,6 +4660,7 @@ int kg_cmaes_wait_termination_fields(kg_cmaes_t h, double *out) {
 }
 
 int kg_cmaes_synchronize(kg_cmaes_t h) {
+  if (flush_consume(h)) return 1;
   KG_HIP(hipStreamSynchronize(h->stream));
   if (h->eigTrace) {
     unsigned long long t[32];
@@ -4556,11 +4844,13 @@ int kg_cmaes_get_sorting_index(kg_cmaes_t h, uint64_t *out) {
 
 int kg_cmaes_get_rng(kg_cmaes_t h, int which, void *state5000) {
   KG_CHECK(which == 0 || which == 1, "rng index must be 0 (Normal) or 1 (Uniform)");
+  if (flush_consume(h)) return 1;
   return (which == 0 ? h->normal : h->uniform).export_gsl(state5000, h->stream);
 }
 
 int kg_cmaes_set_rng(kg_cmaes_t h, int which, const void *state5000) {
   KG_CHECK(which == 0 || which == 1, "rng index must be 0 (Normal) or 1 (Uniform)");
+  if (flush_consume(h)) return 1;  // (ahead of the import: a late consume would advance the new state)
   return (which == 0 ? h->normal : h->uniform).import_gsl(state5000, h->stream);
 }
 

@@ -507,6 +507,55 @@ int kg_tmcmc_set_evaluations(kg_tmcmc_t h, const double *log_prior, const double
  * log-likelihood is not finite are not read.  Also forms the proposal
  * log-density ratios of the acceptance step (:634-677). */
 int kg_tmcmc_set_gradients(kg_tmcmc_t h, const double *grad, const double *fisher);
+/* The Hierarchical/Psi and Hierarchical/ThetaNew log-likelihoods as the
+ * handle's builtin likelihood.  Both are sums over sample
+ * databases that earlier runs left behind, no user model:
+ *
+ *   KG_HIER_PSI       Psi::evaluateLogLikelihood      psi.cpp.base:120-141
+ *                     (+ updateConditionalPriors :110-118): group g is
+ *                     sub-experiment g's "Sample Database" (rows, D columns)
+ *                     and "Sample LogPrior Database" (log_prior); conditional
+ *                     prior k's two parameters are variable param_index[2k],
+ *                     param_index[2k+1] of the evaluated point, or
+ *                     param_const[...] where the index is -1;
+ *   KG_HIER_THETANEW  ThetaNew::evaluateLogLikelihood thetaNew.cpp.base:35-54:
+ *                     one group, the Psi experiment's "Sample Database" (rows,
+ *                     row_width columns); param_index selects database
+ *                     columns; the handle has N = prior_count variables.
+ *
+ * logSumExp is auxiliar/math.hpp:205-225 operation for operation; log and exp
+ * are the correctly rounded ones of the other likelihoods. */
+enum kg_hier_mode { KG_HIER_PSI = 0, KG_HIER_THETANEW = 1 };
+
+typedef struct {
+  int mode;                  /* enum kg_hier_mode */
+  size_t prior_count;        /* D conditional priors (1..128) */
+  const int *kind;           /* D, enum kg_prior_kind */
+  const int *param_index;    /* 2 D: supplier of each prior's first / second parameter, or -1 */
+  const double *param_const; /* 2 D: the parameter where its index is -1 */
+  size_t group_count;        /* G (ThetaNew: 1) */
+  const size_t *group_size;  /* G, each >= 1 */
+  size_t row_width;          /* doubles per row (Psi: D) */
+  const double *rows;        /* sum(group_size) x row_width, row-major, group after group */
+  const double *log_prior;   /* Psi: sum(group_size); ThetaNew: not read */
+} kg_tmcmc_hierarchical;
+
+/* Copies everything to the device; after kg_tmcmc_create and before the first
+ * kg_tmcmc_prepare.  From then on kg_tmcmc_evaluate, the remaining steps of
+ * kg_tmcmc_process / _partial and kg_tmcmc_generation evaluate this likelihood
+ * (replaces the per-sample host call of Hierarchical::evaluateLogPosterior,
+ * hierarchical.cpp.base:34-55; chains with a -inf log-prior are not
+ * evaluated, :39-43).  A conditional prior whose scale parameter is <= 0
+ * (the distributions' updateDistribution checks) or a NaN log-posterior
+ * (:51) is recorded on the device; the next call that waits for the device
+ * (kg_tmcmc_prepare, _process_finalize / _process / _generation,
+ * _synchronize, _get_field, _set_field, _get_rng, _hierarchical_loglik)
+ * returns non-zero with the reference's message and the chain index.
+ * mTMCMC handles are refused. */
+int kg_tmcmc_set_hierarchical(kg_tmcmc_t h, const kg_tmcmc_hierarchical *d);
+/* The same kernel on `rows` arbitrary points X (rows x N, row-major), the
+ * prior not consulted and NaN results returned as they are; waits. */
+int kg_tmcmc_hierarchical_loglik(kg_tmcmc_t h, const double *X, size_t rows, double *out);
 int kg_tmcmc_profile(kg_tmcmc_t h, int enable);
 int kg_tmcmc_profile_read(kg_tmcmc_t h, const char *stage, double *ms_total, size_t *count);
 

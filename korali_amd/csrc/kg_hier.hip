@@ -1,0 +1,269 @@
+// kg_hier.hip — the Hierarchical/Psi and Hierarchical/ThetaNew log-likelihoods
+// (problem/hierarchical/psi/psi.cpp.base:120-141, thetaNew/thetaNew.cpp.base:
+// 35-54) on the device, for kg_tmcmc_* handles.
+//
+// Both are  LL(c) = sum_{g<G} [ LSE_{j<K_g}( base_{g,j} + sum_{k<D} logdens_k ) ]
+// (ThetaNew: G = 1 and -log(M) in front), with logSumExp as auxiliar/math.hpp:
+// 205-225 writes it: max by `>`, +-inf returned as it is, else the exponentials
+// of (v_j - max) added from 0.0 in j order, max + log(sum).
+//
+// One workgroup per (point, group).  Pass 1 forms every v_j (rows strided over
+// the 256 lanes, columns of the database stored one after the other so a
+// wavefront reads consecutive doubles) and reduces the max; NaN never wins a
+// `>` and which of two equal values wins does not change a bit of the result.
+// Pass 2 forms the terms again, one tile of 256 rows at a time, leaves
+// exp_cr(v_j - max) in LDS, and lane 0 adds the tile in row order while the
+// other wavefronts already work on the next tile (two LDS tiles, one barrier
+// per tile).  The P x G group values go to a scratch array; k_hier_finish adds
+// them per point in group order.  Nothing waits on another workgroup and every
+// loop is bounded by a group's size.
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/korali_amd.h"
+#include "kg_common.hpp"
+
+namespace kg {
+namespace hier {
+
+constexpr int MAX_D = 128;  // conditional priors (a TMCMC handle has at most 120 variables)
+constexpr int TPB = 256;    // lanes of a workgroup = rows of a tile
+
+// status word: the first offence, lowest chain first (atomicMin);
+// chain << 32 | code << 16 | conditional prior; code 0 = invalid parameter,
+// 1 = NaN log-posterior of a chain with a finite prior
+constexpr unsigned long long ST_CLEAR = ~0ull;
+
+struct Layout {
+  int mode = 0, D = 0, G = 0, W = 0;  // W: doubles per point (Psi: handle's N; ThetaNew: D)
+  size_t R = 0;                       // rows of all groups
+  int *kind = nullptr;                // D
+  int *psrc = nullptr;                // 2 D: variable / column that supplies the parameter, or -1
+  double *pconst = nullptr;           // 2 D
+  unsigned long long *goff = nullptr; // G + 1 row offsets
+  // Psi: x (D x R), log_cr(x) of the LogNormal columns (D x R), base = -logPrior (R)
+  // ThetaNew: a, b, constant of every (prior, row) (D x R each)
+  double *A = nullptr, *B = nullptr, *Cn = nullptr, *base = nullptr;
+  double *part = nullptr;             // rows x G group values of the last evaluation
+  size_t partRows = 0;
+  double *X = nullptr;                // points of kg_tmcmc_hierarchical_loglik
+  double *out = nullptr;
+  size_t xRows = 0;
+  unsigned long long *status = nullptr, *hStatus = nullptr;
+  const double *lastX = nullptr;      // the points the last evaluation read (device)
+  size_t lastLd = 0;
+  double negLogM = 0.0;               // ThetaNew: -log(M)
+};
+
+// the distributions' updateDistribution constants (uniform.cpp.base:38-44,
+// normal :42, exponential getLogDensity :16, laplace :41, cauchy :41,
+// logNormal :45)
+__device__ inline double prior_const(int kind, double a, double b) {
+  const double pi = 3.14159265358979323846;
+  switch (kind) {
+    case KG_PRIOR_NORMAL:
+    case KG_PRIOR_LOGNORMAL: return -0.5 * log_cr(2 * pi) - log_cr(b);
+    case KG_PRIOR_EXPONENTIAL: return -log_cr(b);
+    case KG_PRIOR_LAPLACE: return -log_cr(2. * b);
+    case KG_PRIOR_CAUCHY: return -log_cr(b * pi);
+    default: return (b - a <= 0.0) ? (double)NAN : -log_cr(b - a);
+  }
+}
+
+__device__ inline bool prior_invalid(int kind, double b) {
+  return (kind == KG_PRIOR_NORMAL || kind == KG_PRIOR_LOGNORMAL || kind == KG_PRIOR_LAPLACE ||
+          kind == KG_PRIOR_CAUCHY) && b <= 0.0;
+}
+
+// getLogDensity of the six distributions; lx = log_cr(x) where kind is LogNormal and x > 0
+__device__ inline double logdens(int kind, double x, double lx, double a, double b, double cn) {
+  switch (kind) {
+    case KG_PRIOR_NORMAL: {
+      const double d = (x - a) / b;
+      return cn - 0.5 * d * d;
+    }
+    case KG_PRIOR_EXPONENTIAL:
+      if (x - a < 0) return -INFINITY;
+      return cn - (x - a) / b;
+    case KG_PRIOR_LAPLACE: return cn - fabs(x - a) / b;
+    case KG_PRIOR_CAUCHY: return cn - log_cr(1. + (x - a) * (x - a) / (b * b));
+    case KG_PRIOR_LOGNORMAL: {
+      if (x <= 0) return -INFINITY;
+      const double d = (lx - a) / b;
+      return cn - lx - 0.5 * d * d;
+    }
+    default: return (x >= a && x <= b) ? cn : -INFINITY;
+  }
+}
+
+// set-up: Psi — log_cr of the LogNormal columns; ThetaNew — every row's
+// parameters and constants
+__global__ void k_hier_setup(int mode, int D, size_t R, int W, const int *__restrict__ kind,
+                             const int *__restrict__ psrc, const double *__restrict__ pconst,
+                             const double *__restrict__ rows, double *__restrict__ A, double *__restrict__ B,
+                             double *__restrict__ Cn) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (size_t)D * R) return;
+  const int k = (int)(e / R);
+  const size_t r = e % R;
+  if (mode == KG_HIER_PSI) {
+    const double x = rows[r * W + k];
+    A[e] = x;
+    B[e] = (kind[k] == KG_PRIOR_LOGNORMAL && x > 0) ? log_cr(x) : 0.0;
+  } else {
+    const double a = psrc[2 * k] >= 0 ? rows[r * W + psrc[2 * k]] : pconst[2 * k];
+    const double b = psrc[2 * k + 1] >= 0 ? rows[r * W + psrc[2 * k + 1]] : pconst[2 * k + 1];
+    A[e] = a;
+    B[e] = b;
+    Cn[e] = prior_const(kind[k], a, b);
+  }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t R, size_t npts, size_t ld,
+                                                   const double *__restrict__ X, const unsigned char *__restrict__ pend,
+                                                   const double *__restrict__ lp, const int *__restrict__ kind,
+                                                   const int *__restrict__ psrc, const double *__restrict__ pconst,
+                                                   const unsigned long long *__restrict__ goff,
+                                                   const double *__restrict__ A, const double *__restrict__ B,
+                                                   const double *__restrict__ Cn, const double *__restrict__ base,
+                                                   double *__restrict__ part, unsigned long long *status) {
+  __shared__ double sa[MAX_D], sb[MAX_D], sc[MAX_D];
+  __shared__ int sk[MAX_D];
+  __shared__ double tile[2][TPB];
+  __shared__ double red[TPB];
+  const size_t c = blockIdx.x / (unsigned)G;
+  const int g = (int)(blockIdx.x % (unsigned)G);
+  if (c >= npts) return;
+  if (pend && !pend[c]) return;
+  if (lp && isinf(lp[c]) && lp[c] < 0) return;  // hierarchical.cpp.base:39-43: not evaluated
+  const int t = threadIdx.x;
+  const double *x = X + c * ld;
+  for (int k = t; k < D; k += TPB) {
+    sk[k] = kind[k];
+    if (MODE == KG_HIER_PSI) {  // updateConditionalPriors (psi.cpp.base:110-118)
+      const double a = psrc[2 * k] >= 0 ? x[psrc[2 * k]] : pconst[2 * k];
+      const double b = psrc[2 * k + 1] >= 0 ? x[psrc[2 * k + 1]] : pconst[2 * k + 1];
+      sa[k] = a;
+      sb[k] = b;
+      sc[k] = prior_const(sk[k], a, b);
+      if (g == 0 && prior_invalid(sk[k], b))
+        atomicMin(status, ((unsigned long long)c << 32) | (unsigned long long)k);
+    } else {  // the point itself and, for LogNormal priors, its logarithm
+      const double v = x[k];
+      sa[k] = v;
+      sb[k] = (sk[k] == KG_PRIOR_LOGNORMAL && v > 0) ? log_cr(v) : 0.0;
+    }
+  }
+  __syncthreads();
+  const size_t r0 = goff[g];
+  const size_t K = goff[g + 1] - r0;
+  auto value = [&](size_t j) -> double {
+    const size_t r = r0 + j;
+    double v;
+    if (MODE == KG_HIER_PSI) {
+      v = base[r];  // psi.cpp.base:132
+      for (int k = 0; k < D; k++) v += logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
+    } else {
+      v = 0.;  // thetaNew.cpp.base:48
+      for (int k = 0; k < D; k++)
+        v += logdens(sk[k], sa[k], sb[k], A[(size_t)k * R + r], B[(size_t)k * R + r], Cn[(size_t)k * R + r]);
+    }
+    return v;
+  };
+  // math.hpp:207-210
+  double m = -INFINITY;
+  for (size_t j = t; j < K; j += TPB) {
+    const double v = value(j);
+    if (v > m) m = v;
+  }
+  red[t] = m;
+  __syncthreads();
+  for (int s = TPB / 2; s > 0; s >>= 1) {
+    if (t < s && red[t + s] > red[t]) red[t] = red[t + s];
+    __syncthreads();
+  }
+  m = red[0];
+  if (isinf(m)) {  // :212-218
+    if (t == 0) part[c * G + g] = m;
+    return;
+  }
+  // :220-224
+  double sum = 0.0;
+  const size_t tiles = (K + TPB - 1) / TPB;
+  for (size_t q = 0; q < tiles; q++) {
+    const size_t j = q * TPB + t;
+    double *buf = tile[q & 1];
+    if (j < K) buf[t] = exp_cr(value(j) - m);
+    __syncthreads();
+    if (t == 0) {
+      const int n = (int)min((size_t)TPB, K - q * TPB);
+      for (int i = 0; i < n; i++) sum += buf[i];
+    }
+  }
+  if (t == 0) part[c * G + g] = m + log_cr(sum);
+}
+
+// psi.cpp.base:124,137 (0.0, += each group) / thetaNew.cpp.base:53
+// (-log(M) + lse); hierarchical.cpp.base:51: a NaN log-posterior is an error
+__global__ void k_hier_finish(int mode, int G, size_t npts, double negLogM, const unsigned char *__restrict__ pend,
+                              const double *__restrict__ lp, const double *__restrict__ part,
+                              double *__restrict__ out, unsigned long long *status) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= npts) return;
+  if (pend && !pend[c]) return;
+  if (lp && isinf(lp[c]) && lp[c] < 0) return;  // k_tm_evaluate left -inf
+  double ll;
+  if (mode == KG_HIER_PSI) {
+    ll = 0.0;
+    for (int g = 0; g < G; g++) ll += part[c * G + g];
+  } else {
+    ll = negLogM + part[c];
+  }
+  out[c] = ll;
+  if (lp && isnan(lp[c] + ll)) atomicMin(status, ((unsigned long long)c << 32) | (1ull << 16));
+}
+
+// -log(M) as thetaNew.cpp.base:53 writes it
+__global__ void k_hier_neglog(double M, double *out) { out[0] = -log_cr(M); }
+
+inline unsigned nblocks(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
+
+// LL of npts points X (ld doubles apart) into out; pend / lp as the handle's
+// pending mask and log-priors, or null (every point, prior not consulted)
+inline int evaluate(Layout &L, const double *X, size_t ld, size_t npts, const unsigned char *pend, const double *lp,
+                    double *out, hipStream_t stream) {
+  if (npts == 0) return 0;
+  KG_CHECK(npts * (size_t)L.G < 0x7fffffffull, "hierarchical likelihood: too many (point, group) pairs");
+  if (L.partRows < npts) {
+    if (L.part) dev_release(L.part, stream);
+    L.part = nullptr;
+    KG_HIP(dev_alloc(&L.part, npts * (size_t)L.G * sizeof(double)));
+    L.partRows = npts;
+  }
+  const unsigned grid = (unsigned)(npts * (size_t)L.G);
+  if (L.mode == KG_HIER_PSI)
+    hipLaunchKernelGGL(k_hier_group<KG_HIER_PSI>, dim3(grid), dim3(TPB), 0, stream, L.D, L.G, L.W, L.R, npts, ld, X,
+                       pend, lp, L.kind, L.psrc, L.pconst, L.goff, L.A, L.B, L.Cn, L.base, L.part, L.status);
+  else
+    hipLaunchKernelGGL(k_hier_group<KG_HIER_THETANEW>, dim3(grid), dim3(TPB), 0, stream, L.D, L.G, L.W, L.R, npts, ld,
+                       X, pend, lp, L.kind, L.psrc, L.pconst, L.goff, L.A, L.B, L.Cn, L.base, L.part, L.status);
+  hipLaunchKernelGGL(k_hier_finish, dim3(nblocks(npts, 128)), dim3(128), 0, stream, L.mode, L.G, npts, L.negLogM, pend,
+                     lp, L.part, out, L.status);
+  KG_HIP(hipGetLastError());
+  L.lastX = X;
+  L.lastLd = ld;
+  return 0;
+}
+
+inline void release(Layout &L) {
+  for (void *p : {(void *)L.kind, (void *)L.psrc, (void *)L.pconst, (void *)L.goff, (void *)L.A, (void *)L.B,
+                  (void *)L.Cn, (void *)L.base, (void *)L.part, (void *)L.X, (void *)L.out, (void *)L.status})
+    if (p) dev_release(p);
+  if (L.hStatus) host_release(L.hStatus);
+  L = Layout();
+}
+
+}  // namespace hier
+}  // namespace kg

@@ -2023,6 +2023,9 @@ struct kg_tmcmc_s {
   double nmRelaunchesD = 0, nmEvalsD = 0, nmRoundsD = 0, nmFallbacksD = 0;  // diagnostics: device-search relaunches after host-exact values  // diagnostics: host-exact cv2 evaluations so far
   double btpeDraws = 0;    // diagnostics: multinomial binomials drawn by BTPE (n p >= 14)
   bool devPending = false;  // accepted count / maxLoglikelihood not yet read back
+  // Hierarchical/Psi or /ThetaNew likelihood (kg_tmcmc_set_hierarchical, kg_hier.hip)
+  hier::Layout *hier = nullptr;
+  bool prepared = false;
   // profiling
   bool profile = false;
   std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
@@ -2079,8 +2082,46 @@ void seed_state(uint64_t seed, unsigned char *out5000) {
 
 inline unsigned nblk(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
-int tm_sync_dev(kg_tmcmc_s *h) {
+// the hierarchical likelihood's status word after a wait: the reference's
+// abort (the distributions' updateDistribution checks,
+// hierarchical.cpp.base:51) as this call's error
+int tm_hier_status(kg_tmcmc_s *h) {
+  hier::Layout &L = *h->hier;
+  const unsigned long long st = *L.hStatus;
+  if (st == hier::ST_CLEAR) return 0;
+  const size_t c = (size_t)(st >> 32);
+  const int code = (int)((st >> 16) & 0xffff), k = (int)(st & 0xffff);
+  *L.hStatus = hier::ST_CLEAR;
+  KG_HIP(hipMemcpyAsync(L.status, L.hStatus, sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
   KG_HIP(hipStreamSynchronize(h->stream));
+  char msg[256];
+  if (code == 1) {
+    snprintf(msg, sizeof msg, "Sample %zu returned NaN logPosterior evaluation.", c);
+  } else {
+    std::vector<int> kind(L.D), psrc(2 * L.D);
+    std::vector<double> pconst(2 * L.D);
+    KG_HIP(hipMemcpy(kind.data(), L.kind, L.D * sizeof(int), hipMemcpyDeviceToHost));
+    KG_HIP(hipMemcpy(psrc.data(), L.psrc, 2 * L.D * sizeof(int), hipMemcpyDeviceToHost));
+    KG_HIP(hipMemcpy(pconst.data(), L.pconst, 2 * L.D * sizeof(double), hipMemcpyDeviceToHost));
+    double v = pconst[2 * k + 1];
+    if (psrc[2 * k + 1] >= 0)
+      KG_HIP(hipMemcpy(&v, L.lastX + c * L.lastLd + psrc[2 * k + 1], sizeof(double), hipMemcpyDeviceToHost));
+    const char *what = kind[k] == KG_PRIOR_NORMAL      ? "Standard Deviation parameter of Normal"
+                       : kind[k] == KG_PRIOR_LOGNORMAL ? "Sigma parameter of LogNormal"
+                       : kind[k] == KG_PRIOR_LAPLACE   ? "Width parameter of Laplace"
+                                                       : "Scale parameter of Cauchy";
+    snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (chain %zu, conditional prior %d)", what, v, c, k);
+  }
+  set_error(msg);
+  return 1;
+}
+
+int tm_sync_dev(kg_tmcmc_s *h) {
+  if (h->hier)
+    KG_HIP(hipMemcpyAsync(h->hier->hStatus, h->hier->status, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  if (h->hier && tm_hier_status(h)) return 1;
   if (h->devPending) {
     h->acceptedSamplesCount = (double)h->hDev->accepted;
     h->maxLoglikelihood = h->hDev->maxLoglikelihood;
@@ -2960,6 +3001,10 @@ int kg_tmcmc_destroy(kg_tmcmc_t h) {
   for (void *p : {(void *)h->hE, (void *)h->hEtail, (void *)h->hW, (void *)h->hNsel, (void *)h->hSrc, (void *)h->hDev, h->hCv, (void *)h->hRec,
                   (void *)h->hSch, (void *)h->hLenD, (void *)h->hNm})
     if (p) host_release(p);
+  if (h->hier) {
+    hier::release(*h->hier);
+    delete h->hier;
+  }
   for (auto *r : h->priorRng) delete r;
   for (auto &t : h->pending) {
     (void)hipEventDestroy(std::get<1>(t));
@@ -3125,6 +3170,7 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
   }
   if (generation == 1 && tm_initialize(h)) return 1;
   if (tm_sync_dev(h)) return 1;
+  h->prepared = true;
   // prepareGeneration :161-170
   h->currentBurnIn = tm_burn_in(h, generation);
   tm_shard_ranges(h);
@@ -3199,10 +3245,137 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
 
 int kg_tmcmc_evaluate(kg_tmcmc_t h) {
   TmStage st(h, "evaluate");
-  hipLaunchKernelGGL(k_tm_evaluate, dim3(nblk(h->P, 128)), dim3(128), 0, h->stream, h->N, h->P, h->cfg.likelihood,
-                     h->cand, h->negLogWidth, h->pmin, h->pmax, h->vkind, h->candLL, h->candLP, h->pend);
+  // a hierarchical handle: the log-priors (and -inf log-likelihoods below a
+  // -inf prior) here, the likelihood of the other pending chains after it
+  hipLaunchKernelGGL(k_tm_evaluate, dim3(nblk(h->P, 128)), dim3(128), 0, h->stream, h->N, h->P,
+                     h->hier ? -1 : h->cfg.likelihood, h->cand, h->negLogWidth, h->pmin, h->pmax, h->vkind, h->candLL,
+                     h->candLP, h->pend);
   KG_HIP(hipGetLastError());
+  if (h->hier) {
+    TmStage sh(h, "hier_loglik");
+    return hier::evaluate(*h->hier, h->cand, (size_t)h->N, (size_t)h->P, h->pend, h->candLP, h->candLL, h->stream);
+  }
   return 0;
+}
+
+int kg_tmcmc_set_hierarchical(kg_tmcmc_t h, const kg_tmcmc_hierarchical *d) {
+  KG_CHECK(h && d, "kg_tmcmc_set_hierarchical: null argument");
+  KG_CHECK(!h->mt, "Hierarchical problems run with Version 'TMCMC' (mTMCMC needs gradients)");
+  KG_CHECK(!h->hier, "kg_tmcmc_set_hierarchical: the handle already has a hierarchical likelihood");
+  KG_CHECK(!h->prepared, "kg_tmcmc_set_hierarchical: call before the first kg_tmcmc_prepare");
+  KG_CHECK(d->mode == KG_HIER_PSI || d->mode == KG_HIER_THETANEW,
+           "kg_tmcmc_set_hierarchical: mode must be KG_HIER_PSI or KG_HIER_THETANEW");
+  KG_CHECK(d->prior_count >= 1 && d->prior_count <= (size_t)hier::MAX_D,
+           "kg_tmcmc_set_hierarchical: 1..128 conditional priors");
+  KG_CHECK(d->kind && d->param_index && d->param_const && d->group_size && d->rows,
+           "kg_tmcmc_set_hierarchical: null array");
+  const int D = (int)d->prior_count, N = h->N;
+  const bool psi = d->mode == KG_HIER_PSI;
+  KG_CHECK(d->row_width >= 1 && d->row_width <= 65536, "kg_tmcmc_set_hierarchical: row_width out of range");
+  if (psi) {
+    KG_CHECK(d->log_prior, "kg_tmcmc_set_hierarchical: Psi needs the sub-experiments' log-priors");
+    KG_CHECK(d->row_width == (size_t)D, "kg_tmcmc_set_hierarchical: Psi rows have one column per conditional prior");
+    KG_CHECK(d->group_count >= 1, "kg_tmcmc_set_hierarchical: at least one group");
+  } else {
+    KG_CHECK(N == D, "Hierarchical/ThetaNew: the handle must have as many variables as conditional priors");
+    KG_CHECK(d->group_count == 1, "kg_tmcmc_set_hierarchical: ThetaNew has one group (the Psi database)");
+  }
+  KG_CHECK(d->group_count <= (size_t)1 << 20, "kg_tmcmc_set_hierarchical: too many groups");
+  const int lim = psi ? N : (int)d->row_width;
+  for (int k = 0; k < D; k++) {
+    KG_CHECK(d->kind[k] >= KG_PRIOR_UNIFORM && d->kind[k] <= KG_PRIOR_LOGNORMAL,
+             "kg_tmcmc_set_hierarchical: kind entries must be KG_PRIOR_UNIFORM .. KG_PRIOR_LOGNORMAL");
+    for (int q = 0; q < 2; q++)
+      KG_CHECK(d->param_index[2 * k + q] >= -1 && d->param_index[2 * k + q] < lim,
+               "kg_tmcmc_set_hierarchical: param_index out of range");
+  }
+  std::vector<unsigned long long> goff(d->group_count + 1, 0);
+  for (size_t g = 0; g < d->group_count; g++) {
+    KG_CHECK(d->group_size[g] >= 1, "kg_tmcmc_set_hierarchical: a group size of 0");
+    KG_CHECK(d->group_size[g] <= (size_t)1 << 40, "kg_tmcmc_set_hierarchical: group size out of range");
+    goff[g + 1] = goff[g] + d->group_size[g];
+  }
+  const size_t R = goff.back(), W = d->row_width;
+  if (!psi) {
+    // a database row with an invalid scale parameter: the reference aborts at
+    // the first evaluation (updateConditionalPriors, thetaNew.cpp.base:46)
+    for (size_t r = 0; r < R; r++)
+      for (int k = 0; k < D; k++) {
+        const int kd = d->kind[k], ix = d->param_index[2 * k + 1];
+        const double b = ix >= 0 ? d->rows[r * W + ix] : d->param_const[2 * k + 1];
+        if ((kd == KG_PRIOR_NORMAL || kd == KG_PRIOR_LOGNORMAL || kd == KG_PRIOR_LAPLACE || kd == KG_PRIOR_CAUCHY) &&
+            b <= 0.0) {
+          char msg[200];
+          snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (Psi sample %zu, conditional prior %d)",
+                   kd == KG_PRIOR_NORMAL      ? "Standard Deviation parameter of Normal"
+                   : kd == KG_PRIOR_LOGNORMAL ? "Sigma parameter of LogNormal"
+                   : kd == KG_PRIOR_LAPLACE   ? "Width parameter of Laplace"
+                                              : "Scale parameter of Cauchy",
+                   b, r, k);
+          KG_CHECK(false, msg);
+        }
+      }
+  }
+  KG_HIP(hipSetDevice(h->cfg.device));
+  auto *L = new hier::Layout();
+  h->hier = L;  // released by kg_tmcmc_destroy, also after an error below
+  L->mode = d->mode;
+  L->D = D;
+  L->G = (int)d->group_count;
+  L->W = (int)W;
+  L->R = R;
+  const size_t DR = (size_t)D * R;
+  double *rowsDev = nullptr;
+  int rc = tdalloc(&L->kind, D) | tdalloc(&L->psrc, 2 * D) | tdalloc(&L->pconst, 2 * D) |
+           tdalloc(&L->goff, goff.size()) | tdalloc(&L->A, DR) | tdalloc(&L->B, DR) | tdalloc(&L->Cn, psi ? 1 : DR) |
+           tdalloc(&L->base, psi ? R : 1) | tdalloc(&L->status, 1) | tdalloc(&rowsDev, R * W);
+  if (rc) {
+    if (rowsDev) dev_release(rowsDev);
+    return 1;
+  }
+  KG_HIP(host_alloc(&L->hStatus, sizeof(unsigned long long), hipHostMallocDefault));
+  *L->hStatus = hier::ST_CLEAR;
+  KG_HIP(hipMemcpy(L->status, L->hStatus, sizeof(unsigned long long), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->kind, d->kind, D * sizeof(int), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->psrc, d->param_index, 2 * D * sizeof(int), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->pconst, d->param_const, 2 * D * sizeof(double), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->goff, goff.data(), goff.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(rowsDev, d->rows, R * W * sizeof(double), hipMemcpyHostToDevice));
+  if (psi) {
+    std::vector<double> base(R);
+    for (size_t r = 0; r < R; r++) base[r] = -d->log_prior[r];  // psi.cpp.base:132
+    KG_HIP(hipMemcpy(L->base, base.data(), R * sizeof(double), hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(hier::k_hier_setup, dim3(nblk(DR, 256)), dim3(256), 0, h->stream, L->mode, D, R, (int)W, L->kind,
+                     L->psrc, L->pconst, rowsDev, L->A, L->B, L->Cn);
+  if (!psi) hipLaunchKernelGGL(hier::k_hier_neglog, dim3(1), dim3(1), 0, h->stream, (double)R, L->base);
+  KG_HIP(hipGetLastError());
+  if (!psi) KG_HIP(hipMemcpyAsync(&L->negLogM, L->base, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  dev_release(rowsDev);
+  return 0;
+}
+
+int kg_tmcmc_hierarchical_loglik(kg_tmcmc_t h, const double *X, size_t rows, double *out) {
+  KG_CHECK(h && h->hier, "kg_tmcmc_hierarchical_loglik: the handle has no hierarchical likelihood");
+  KG_CHECK(rows == 0 || (X && out), "kg_tmcmc_hierarchical_loglik: null argument");
+  if (rows == 0) return 0;
+  hier::Layout &L = *h->hier;
+  const size_t N = (size_t)h->N;
+  if (tm_sync_dev(h)) return 1;
+  if (L.xRows < rows) {
+    if (L.X) dev_release(L.X);
+    if (L.out) dev_release(L.out);
+    L.X = L.out = nullptr;
+    L.xRows = 0;
+    KG_HIP(dev_alloc(&L.X, rows * N * sizeof(double)));
+    KG_HIP(dev_alloc(&L.out, rows * sizeof(double)));
+    L.xRows = rows;
+  }
+  KG_HIP(hipMemcpyAsync(L.X, X, rows * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (hier::evaluate(L, L.X, N, rows, nullptr, nullptr, L.out, h->stream)) return 1;
+  KG_HIP(hipMemcpyAsync(out, L.out, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return tm_sync_dev(h);
 }
 
 int kg_tmcmc_evaluate_prior(kg_tmcmc_t h) {

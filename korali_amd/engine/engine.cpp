@@ -569,6 +569,9 @@ const KeyList OPTIMIZATION_KEYS = {"Type", "Num Objectives", "Objective Function
                                    "Has Discrete Variables", "Objective Kernel"};
 const KeyList BAYESIAN_CUSTOM_KEYS = {"Type", "Likelihood Model", "Likelihood Kernel"};
 const KeyList BAYESIAN_REFERENCE_KEYS = {"Type", "Computational Model", "Reference Data", "Likelihood Model"};
+// hierarchical/psi/psi.config, hierarchical/thetaNew/thetaNew.config
+const KeyList HIERARCHICAL_PSI_KEYS = {"Type", "Sub Experiments", "Conditional Priors"};
+const KeyList HIERARCHICAL_THETANEW_KEYS = {"Type", "Psi Experiment"};
 
 void rejectProblemUnrecognised(Json &pb, const std::string &canonType);
 
@@ -597,6 +600,188 @@ void rejectProblemUnrecognised(Json &pb, const std::string &pt) {
   if (pt == "optimization") rejectUnrecognised(pb, "Optimization", {OPTIMIZATION_KEYS}, {});
   else if (pt == "bayesian/custom") rejectUnrecognised(pb, "Custom", {BAYESIAN_CUSTOM_KEYS}, {});
   else if (pt == "bayesian/reference") rejectUnrecognised(pb, "Reference", {BAYESIAN_REFERENCE_KEYS}, {});
+  else if (pt == "hierarchical/psi") rejectUnrecognised(pb, "Psi", {HIERARCHICAL_PSI_KEYS}, {});
+  else if (pt == "hierarchical/thetanew") rejectUnrecognised(pb, "ThetaNew", {HIERARCHICAL_THETANEW_KEYS}, {});
+}
+
+// ---------------------------------------------------- hierarchical problems
+// Hierarchical/Psi and Hierarchical/ThetaNew (problem/hierarchical/psi/
+// psi.cpp.base, thetaNew/thetaNew.cpp.base): their log-likelihoods are sums
+// over the sample databases of finished experiments, evaluated on the device
+// (kg_tmcmc_set_hierarchical).  Everything below reads the configuration and
+// raises the reference's initialize() errors; no device call.
+struct PriorKind {
+  const char *type, *a, *b, *what;
+  int kind;
+};
+const PriorKind PRIOR_KINDS[] = {
+    {"univariate/uniform", "Minimum", "Maximum", nullptr, KG_PRIOR_UNIFORM},
+    {"univariate/normal", "Mean", "Standard Deviation", "Standard Deviation parameter of Normal", KG_PRIOR_NORMAL},
+    {"univariate/exponential", "Location", "Mean", nullptr, KG_PRIOR_EXPONENTIAL},
+    {"univariate/laplace", "Mean", "Width", "Width parameter of Laplace", KG_PRIOR_LAPLACE},
+    {"univariate/cauchy", "Location", "Scale", "Scale parameter of Cauchy", KG_PRIOR_CAUCHY},
+    {"univariate/lognormal", "Mu", "Sigma", "Sigma parameter of LogNormal", KG_PRIOR_LOGNORMAL}};
+
+struct HierarchicalSpec {
+  int mode = KG_HIER_PSI;
+  std::vector<int> kinds, index;
+  std::vector<double> constants, rows, logPriors;
+  std::vector<size_t> groupSizes;
+  size_t width = 0;
+};
+
+const Json *member(const Json &j, const char *key) {
+  return j.is_object() && j.contains(key) ? &j.at(key) : nullptr;
+}
+
+// Psi::initialize :13-30 and :73-107 on the experiment `ex` that owns the
+// conditional priors (its Distributions and Variables): a property that is a
+// string names one of ex's variables, a number is a constant
+void readConditionalPriors(const Json &ex, const Json *names, HierarchicalSpec &hs) {
+  if (!names || !names->is_array() || names->size() == 0)
+    fail("Hierarchical Bayesian (Psi) problems require at least one conditional prior\n");
+  const Json *ds = member(ex, "Distributions"), *vs = member(ex, "Variables");
+  const size_t D = names->size();
+  std::vector<const Json *> dist(D, nullptr);
+  for (size_t i = 0; i < D; i++) {
+    const std::string name = names->at(i).is_string() ? names->at(i).getString() : std::string();
+    for (size_t j = 0; ds && ds->is_array() && j < ds->size(); j++) {
+      const Json *n = member(ds->at(j), "Name");
+      if (n && n->is_string() && n->getString() == name) dist[i] = &ds->at(j);
+    }
+    if (!dist[i]) fail("Did not find conditional prior distribution %s\n", name.c_str());
+  }
+  for (size_t i = 0; i < D; i++) {
+    const Json *t = member(*dist[i], "Type");
+    const std::string dt = t && t->is_string() ? canon(t->getString()) : std::string();
+    const PriorKind *kd = nullptr;
+    for (const PriorKind &q : PRIOR_KINDS)
+      if (dt == q.type) kd = &q;
+    if (!kd)
+      fail("Conditional priors are 'Univariate/Uniform', 'Univariate/Normal', 'Univariate/Exponential', "
+           "'Univariate/Laplace', 'Univariate/Cauchy' or 'Univariate/LogNormal' distributions (distribution '%s' is '%s').",
+           names->at(i).getString().c_str(), dt.c_str());
+    hs.kinds.push_back(kd->kind);
+    for (const char *key : {kd->a, kd->b}) {
+      const Json *v = member(*dist[i], key);
+      if (!v || v->is_null())
+        fail(" + No value provided for mandatory setting: ['%s'] required by Distributions.\n", key);
+      if (v->is_string()) {
+        int position = -1;
+        for (size_t k = 0; vs && vs->is_array() && k < vs->size(); k++) {
+          const Json *n = member(vs->at(k), "Name");
+          if (n && n->is_string() && n->getString() == v->getString()) position = (int)k;
+        }
+        if (position < 0)
+          fail("No variable name specified that satisfies conditional prior property \"%s\" with key: \"%s\".\n", key,
+               v->getString().c_str());
+        hs.index.push_back(position);
+        hs.constants.push_back(0.0);
+      } else if (v->is_number()) {
+        hs.index.push_back(-1);
+        hs.constants.push_back(v->getDouble());
+      } else {
+        fail("Conditional prior property \"%s\" must be a number or the name of a variable.\n", key);
+      }
+    }
+  }
+}
+
+// the three sample databases of a finished sampling experiment (psi.cpp.base:
+// 52-71; the non-finite prior check covers every entry, the reference's loop
+// bound only the first few)
+bool readDatabases(const Json &ex, size_t width, std::vector<double> &rows, std::vector<double> &lp, size_t &count) {
+  const Json *sv = member(ex, "Solver");
+  if (!sv) return false;
+  const Json *jlp = member(*sv, "Sample LogPrior Database"), *jll = member(*sv, "Sample LogLikelihood Database"),
+             *jdb = member(*sv, "Sample Database");
+  if (!jlp || !jll || !jdb || !jlp->is_array() || !jll->is_array() || !jdb->is_array()) return false;
+  count = jdb->size();
+  if (count == 0 || jlp->size() != count || jll->size() != count) return false;
+  try {
+    const std::vector<double> p = jlp->getDoubleVector();
+    (void)jll->getDoubleVector();
+    for (size_t j = 0; j < count; j++) {
+      const Json &r = jdb->at(j);
+      if (!r.is_array() || r.size() != width) return false;
+      const std::vector<double> x = r.getDoubleVector();
+      rows.insert(rows.end(), x.begin(), x.end());
+    }
+    lp.insert(lp.end(), p.begin(), p.end());
+  } catch (const std::exception &) {
+    return false;
+  }
+  return true;
+}
+
+bool finished(const Json &ex) {
+  const Json *f = member(ex, "Is Finished");
+  return f && f->is_bool() && f->getBool();
+}
+
+void readPsi(const Json &js, HierarchicalSpec &hs) {
+  const Json &pb = js.at("Problem");
+  hs.mode = KG_HIER_PSI;
+  readConditionalPriors(js, member(pb, "Conditional Priors"), hs);
+  const size_t D = hs.kinds.size();
+  const Json *subs = member(pb, "Sub Experiments");
+  if (!subs || !subs->is_array() || subs->size() < 2)
+    fail("Hierarchical Bayesian (Psi) problem requires defining at least two executed sub-problems.\n");
+  for (size_t i = 0; i < subs->size(); i++) {
+    const Json *v = member(subs->at(i), "Variables");
+    const size_t nv = v && v->is_array() ? v->size() : 0;
+    if (nv != D)
+      fail("Sub-problem %lu contains a different number of variables (%lu) than conditional priors in the "
+           "Hierarchical Bayesian (Psi) problem (%lu).\n", (unsigned long)i, (unsigned long)nv, (unsigned long)D);
+    if (!finished(subs->at(i)))
+      fail("The Hierarchical Bayesian (Psi) requires that all problems have run completely, but Problem %lu has "
+           "not.\n", (unsigned long)i);
+  }
+  hs.width = D;
+  for (size_t i = 0; i < subs->size(); i++) {
+    size_t count = 0;
+    const size_t first = hs.logPriors.size();
+    if (!readDatabases(subs->at(i), D, hs.rows, hs.logPriors, count))
+      fail("Error reading the sample database from sub-problem: %lu. Was it a sampling experiment?\n", (unsigned long)i);
+    hs.groupSizes.push_back(count);
+    for (size_t j = 0; j < count; j++) {
+      const double expPrior = std::exp(hs.logPriors[first + j]);
+      if (!std::isfinite(expPrior))
+        fail("Non finite (%lf) prior has been detected at sample %zu in subproblem %zu.\n", expPrior, j, i);
+    }
+  }
+}
+
+void readThetaNew(const Json &js, size_t variableCount, HierarchicalSpec &hs) {
+  const Json &pb = js.at("Problem");
+  hs.mode = KG_HIER_THETANEW;
+  const Json *psi = member(pb, "Psi Experiment");
+  const Json *ppb = psi ? member(*psi, "Problem") : nullptr;
+  const Json *ptype = ppb ? member(*ppb, "Type") : nullptr;
+  if (!ptype || !ptype->is_string() || canon(ptype->getString()) != "hierarchical/psi")
+    fail("The Hierarchical Bayesian (Theta New) requires a 'Psi Experiment' whose problem is of type "
+         "'Hierarchical/Psi'.\n");
+  if (!finished(*psi))
+    fail("The Hierarchical Bayesian (Theta New) requires that the psi-problem has run completely, but it has not.\n");
+  readConditionalPriors(*psi, member(*ppb, "Conditional Priors"), hs);
+  const Json *pv = member(*psi, "Variables");
+  hs.width = pv && pv->is_array() ? pv->size() : 0;
+  size_t count = 0;
+  if (hs.width == 0 || !readDatabases(*psi, hs.width, hs.rows, hs.logPriors, count))
+    fail("Error reading the sample database from the psi-problem. Was it a sampling experiment?\n");
+  const Json *leaders = member(psi->at("Solver"), "Chain Leaders LogLikelihoods");
+  if (!leaders || !leaders->is_array() || leaders->size() != count)
+    fail("The psi-problem's 'Chain Leaders LogLikelihoods' (%zu) and 'Sample Database' (%zu) differ in length.\n",
+         leaders && leaders->is_array() ? leaders->size() : (size_t)0, count);
+  hs.groupSizes.push_back(count);
+  for (size_t j = 0; j < count; j++) {
+    const double expPrior = std::exp(hs.logPriors[j]);
+    if (!std::isfinite(expPrior))
+      fail("Non finite (%lf) prior has been detected at sample %zu in subproblem.\n", expPrior, j);
+  }
+  if (variableCount != hs.kinds.size())
+    fail("The Hierarchical Bayesian (Theta New) problem has %zu variables, the psi-problem %zu conditional priors; "
+         "they must be as many.\n", variableCount, hs.kinds.size());
 }
 
 // ------------------------------------------------------------- sharding
@@ -1263,7 +1448,8 @@ struct TmcmcModule : SolverModule {
     Json &sv = js["Solver"];
     Json &pb = js["Problem"];
     const std::string pt = canon(str(pb, "Type", ""));
-    if (pt != "bayesian/custom" && pt != "bayesian/reference")
+    const bool hierarchical = pt == "hierarchical/psi" || pt == "hierarchical/thetanew";
+    if (pt != "bayesian/custom" && pt != "bayesian/reference" && !hierarchical)
       fail("The device TMCMC path supports problems of type 'Bayesian/Custom' and 'Bayesian/Reference' (is '%s').",
            pb["Type"].getString().c_str());
     rejectUnrecognised(sv, "TMCMC", {SOLVER_KEYS, TMCMC_KEYS}, {SOLVER_TERMINATION, TMCMC_TERMINATION});
@@ -1279,6 +1465,9 @@ struct TmcmcModule : SolverModule {
     if (mtmcmc && !reference) fail("mTMCMC works only for problems of type 'Bayesian/Reference'\n");
     std::vector<VariableSpec> vars = readVariables(js);
     N = vars.size();
+    HierarchicalSpec hs;
+    if (pt == "hierarchical/psi") readPsi(js, hs);
+    if (pt == "hierarchical/thetanew") readThetaNew(js, N, hs);
     P = uint(sv, "Population Size", 0);
     if (P < 2) fail("TMCMC 'Population Size' must be at least 2.");
     const double mcl = num(sv, "Max Chain Length", 1);
@@ -1318,18 +1507,8 @@ struct TmcmcModule : SolverModule {
         // the two parameters of each supported distribution and its
         // updateDistribution check (exponential.cpp.base has none: a Mean <= 0
         // is accepted, its log-density is then NaN / infinite as the reference's)
-        struct Kind {
-          const char *type, *a, *b, *what;
-          int kind;
-        };
-        static const Kind kinds[] = {
-            {"univariate/normal", "Mean", "Standard Deviation", "Standard Deviation parameter of Normal", KG_PRIOR_NORMAL},
-            {"univariate/exponential", "Location", "Mean", nullptr, KG_PRIOR_EXPONENTIAL},
-            {"univariate/laplace", "Mean", "Width", "Width parameter of Laplace", KG_PRIOR_LAPLACE},
-            {"univariate/cauchy", "Location", "Scale", "Scale parameter of Cauchy", KG_PRIOR_CAUCHY},
-            {"univariate/lognormal", "Mu", "Sigma", "Sigma parameter of LogNormal", KG_PRIOR_LOGNORMAL}};
-        const Kind *kd = nullptr;
-        for (const Kind &q : kinds)
+        const PriorKind *kd = nullptr;
+        for (const PriorKind &q : PRIOR_KINDS)
           if (dt == q.type) kd = &q;
         if (!kd)
           fail("The device TMCMC path supports 'Univariate/Uniform', 'Univariate/Normal', 'Univariate/Exponential', "
@@ -1342,7 +1521,9 @@ struct TmcmcModule : SolverModule {
       }
       pdist[i] = k;
     }
-    if (reference) {
+    if (hierarchical) {
+      builtin = true;  // no host callback, no 'Computational Model'
+    } else if (reference) {
       // Reference::initialize (reference.cpp.base:17-23) + the model checks
       // of evaluateLoglikelihood (:25-44)
       if (!pb.contains("Computational Model") || !pb["Computational Model"].is_integer())
@@ -1403,6 +1584,20 @@ struct TmcmcModule : SolverModule {
         fail("Domain Extension Factor lower than 0.0 (is %lf)\n", c.domain_extension_factor);
     }
     check(kg_tmcmc_create(&c, &h));
+    if (hierarchical) {
+      kg_tmcmc_hierarchical d{};
+      d.mode = hs.mode;
+      d.prior_count = hs.kinds.size();
+      d.kind = hs.kinds.data();
+      d.param_index = hs.index.data();
+      d.param_const = hs.constants.data();
+      d.group_count = hs.groupSizes.size();
+      d.group_size = hs.groupSizes.data();
+      d.row_width = hs.width;
+      d.rows = hs.rows.data();
+      d.log_prior = hs.logPriors.data();
+      check(kg_tmcmc_set_hierarchical(h, &d));
+    }
     unsigned char st[5000];
     if (seeds.range(gm, st)) check(kg_tmcmc_set_rng(h, 0, st));
     if (seeds.range(gv, st)) check(kg_tmcmc_set_rng(h, 1, st));
@@ -1645,6 +1840,9 @@ std::vector<std::vector<float>> Experiment::getEvaluation(const std::vector<std:
 Experiment::~Experiment() = default;
 Experiment::Experiment(Experiment &&) noexcept = default;
 Experiment &Experiment::operator=(Experiment &&) noexcept = default;
+
+// e["Problem"]["Sub Experiments"][i] = subExperiment: a copy of its JSON
+Json &Json::operator=(const Experiment &e) { return *this = e._js; }
 
 bool Experiment::loadState(const std::string &path) {
   std::ifstream f(path);
@@ -2480,6 +2678,22 @@ void runExperiment(Experiment &e, Conduit &conduit) {
   const std::string stype = canon(sv["Type"].getString());
   TmcmcModule *tm = nullptr;
   Collective *dist = conduit.dist.get();
+  {
+    // hierarchical problems: Psi and ThetaNew are closed-form sums on the
+    // device under TMCMC; Theta needs the sub-problem's computational model
+    const Json &cjs = js;
+    const Json *pbt = cjs.contains("Problem") ? member(cjs.at("Problem"), "Type") : nullptr;
+    const std::string ptype = pbt && pbt->is_string() ? canon(pbt->getString()) : std::string();
+    if (ptype.rfind("hierarchical/", 0) == 0) {
+      if (ptype != "hierarchical/psi" && ptype != "hierarchical/thetanew")
+        fail("Problem type '%s' is not provided: of the hierarchical problems the device path supports "
+             "'Hierarchical/Psi' and 'Hierarchical/ThetaNew' ('Hierarchical/Theta' needs the sub-problem's "
+             "computational model).", pbt->getString().c_str());
+      if (stype != "sampler/tmcmc" && stype != "tmcmc")
+        fail("Problems of type '%s' are supported with the 'Sampler/TMCMC' solver (is '%s').",
+             pbt->getString().c_str(), sv["Type"].getString().c_str());
+    }
+  }
   // the solver goes with the run, failed or not: its device handle, and a
   // host environment's coroutines, which must unwind while the caller (the
   // Python binding) has the GIL released

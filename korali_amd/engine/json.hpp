@@ -23,6 +23,7 @@
 namespace korali {
 
 class Sample;
+class Experiment;
 using Function = std::function<void(Sample &)>;
 
 // process-wide table of user functions; JSON stores their index
@@ -83,6 +84,9 @@ class Json {
     }
     return *this;
   }
+  // an Experiment as a value (Hierarchical problems' "Sub Experiments" /
+  // "Psi Experiment"): a copy of its JSON (engine.cpp)
+  Json &operator=(const Experiment &e);
   ~Json() { release(); }
   void swap(Json &o) noexcept {
     std::swap(t_, o.t_);

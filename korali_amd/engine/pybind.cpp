@@ -51,6 +51,8 @@ Json toJson(const py::handle &o) {
     Json v;
     if (jsonRefValue(o, v)) return v;
   }
+  // an Experiment as a value (e["Problem"]["Sub Experiments"][i] = sub): its JSON
+  if (py::isinstance<korali::Experiment>(o)) return o.cast<const korali::Experiment &>()._js;
   if (py::isinstance<py::bool_>(o)) return Json(o.cast<bool>());
   if (py::isinstance<py::int_>(o)) {
     const py::int_ i = py::reinterpret_borrow<py::int_>(o);

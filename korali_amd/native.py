@@ -67,6 +67,19 @@ class _TmcmcCfg(C.Structure):
     ]
 
 
+class _TmcmcHierarchical(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int), ("prior_count", C.c_size_t), ("kind", C.POINTER(C.c_int)),
+        ("param_index", C.POINTER(C.c_int)), ("param_const", C.POINTER(C.c_double)),
+        ("group_count", C.c_size_t), ("group_size", C.POINTER(C.c_size_t)), ("row_width", C.c_size_t),
+        ("rows", C.POINTER(C.c_double)), ("log_prior", C.POINTER(C.c_double)),
+    ]
+
+
+HIER_MODES = {"psi": 0, "thetanew": 1}
+PRIOR_KINDS = {"uniform": 0, "normal": 1, "exponential": 2, "laplace": 3, "cauchy": 4, "lognormal": 5}
+
+
 class _DeaCfg(C.Structure):
     _fields_ = [
         ("variable_count", C.c_size_t), ("population_size", C.c_size_t),
@@ -100,7 +113,7 @@ EXPORTED = [
     "kg_tmcmc_get_field", "kg_tmcmc_set_field", "kg_tmcmc_get_rng", "kg_tmcmc_set_rng", "kg_tmcmc_prepare",
     "kg_tmcmc_evaluate", "kg_tmcmc_process", "kg_tmcmc_advance", "kg_tmcmc_get_pending",
     "kg_tmcmc_process_partial", "kg_tmcmc_process_finalize", "kg_tmcmc_device_ptr", "kg_tmcmc_stream", "kg_tmcmc_evaluate_prior", "kg_tmcmc_get_candidates", "kg_tmcmc_set_evaluations",
-    "kg_tmcmc_set_gradients",
+    "kg_tmcmc_set_gradients", "kg_tmcmc_set_hierarchical", "kg_tmcmc_hierarchical_loglik",
     "kg_tmcmc_profile", "kg_tmcmc_profile_read", "kg_debug_mt_jump", "kg_debug_multinomial", "kg_debug_cartpole",
     "kg_debug_cartpole_at",
     "kg_debug_host_tridiag", "kg_debug_host_chase",
@@ -195,6 +208,8 @@ def lib():
         L.kg_tmcmc_get_candidates.argtypes = [vp, dp, sz]
         L.kg_tmcmc_set_evaluations.argtypes = [vp, dp, dp]
         L.kg_tmcmc_set_gradients.argtypes = [vp, dp, dp]
+        L.kg_tmcmc_set_hierarchical.argtypes = [vp, C.POINTER(_TmcmcHierarchical)]
+        L.kg_tmcmc_hierarchical_loglik.argtypes = [vp, dp, sz, dp]
         L.kg_tmcmc_advance.argtypes = [vp, sz, C.POINTER(sz)]
         L.kg_tmcmc_get_pending.argtypes = [vp, C.POINTER(C.c_ubyte)]
         L.kg_tmcmc_profile.argtypes = [vp, ip]
@@ -685,6 +700,48 @@ class TmcmcDevice:
         if g.size != self.P * self.N or f.size != self.P * self.N * self.N:
             raise ValueError("set_gradients: expected P x N gradients and P x N x N Fisher informations")
         check(self._L.kg_tmcmc_set_gradients(self.h, _dptr(g), _dptr(f)))
+
+    def set_hierarchical(self, mode, kinds, param_index, param_const, groups, log_priors=None):
+        """The Hierarchical/Psi ("psi") or /ThetaNew ("thetanew") likelihood as
+        this handle's builtin one (kg_tmcmc_set_hierarchical), before the first
+        prepare.  kinds: D prior kinds (names or enum kg_prior_kind);
+        param_index / param_const: D x 2, the variable (Psi) or database column
+        (ThetaNew) that supplies each parameter, or -1 and the constant; groups:
+        the sample databases (K_g x width each; ThetaNew: one); log_priors:
+        Psi, each group's K_g log-priors."""
+        d = _TmcmcHierarchical()
+        d.mode = HIER_MODES[mode.lower()] if isinstance(mode, str) else int(mode)
+        kd = np.ascontiguousarray([PRIOR_KINDS[k.lower()] if isinstance(k, str) else int(k) for k in kinds],
+                                  dtype=np.int32)
+        D = kd.size
+        ix = np.ascontiguousarray(param_index, dtype=np.int32).reshape(-1)
+        cs = np.ascontiguousarray(param_const, dtype=np.float64).reshape(-1)
+        if ix.size != 2 * D or cs.size != 2 * D:
+            raise ValueError("set_hierarchical: param_index / param_const must be D x 2")
+        gs = [np.ascontiguousarray(g, dtype=np.float64) for g in groups]
+        if any(g.ndim != 2 for g in gs) or len({g.shape[1] for g in gs}) != 1:
+            raise ValueError("set_hierarchical: groups must be 2-D arrays of one width")
+        sizes = np.ascontiguousarray([g.shape[0] for g in gs], dtype=np.uintp)
+        rows = np.ascontiguousarray(np.concatenate(gs, axis=0))
+        d.prior_count, d.kind = D, kd.ctypes.data_as(C.POINTER(C.c_int))
+        d.param_index, d.param_const = ix.ctypes.data_as(C.POINTER(C.c_int)), _dptr(cs)
+        d.group_count, d.group_size = len(gs), sizes.ctypes.data_as(C.POINTER(C.c_size_t))
+        d.row_width, d.rows = gs[0].shape[1], _dptr(rows)
+        lp = None
+        if log_priors is not None:
+            lp = np.ascontiguousarray(np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1) for v in log_priors]))
+            if lp.size != rows.shape[0]:
+                raise ValueError("set_hierarchical: one log-prior per database row")
+            d.log_prior = _dptr(lp)
+        check(self._L.kg_tmcmc_set_hierarchical(self.h, C.byref(d)))
+
+    def hierarchical_loglik(self, X):
+        """The hierarchical log-likelihood of arbitrary points (rows x N), the
+        prior not consulted (kg_tmcmc_hierarchical_loglik)."""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, self.N)
+        out = np.empty(X.shape[0])
+        check(self._L.kg_tmcmc_hierarchical_loglik(self.h, _dptr(X), X.shape[0], _dptr(out)))
+        return out
 
     def field_size(self, name):
         n = C.c_size_t()

@@ -43,8 +43,12 @@ def launch(tmp_path, ranks, solver, model, transport, cov):
                str(tmp_path), solver, model, transport, cov]
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
         # the port was free when probed; another process can take it before the
-        # launcher's rendezvous listens (no rank has started then): pick another
-        if r.returncode == 0 or not ("EADDRINUSE" in r.stderr and "next_rendezvous" in r.stderr):
+        # launcher's rendezvous listens (no rank has started then): pick another.
+        # Likewise the conduit's bootstrap port (master port + 1), which is not
+        # probed: rank 0 fails to bind it before any collective has run
+        taken = ("EADDRINUSE" in r.stderr and "next_rendezvous" in r.stderr) or \
+            "cannot bind the bootstrap port" in r.stderr + r.stdout
+        if r.returncode == 0 or not taken:
             break
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return [json.load(open(tmp_path / f"rank{k}.json")) for k in range(ranks)]

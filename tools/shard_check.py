@@ -10,7 +10,9 @@ the unsharded exact run (the reference's trajectory, which the unsharded
 handle reproduces bit for bit, tests/test_gpu_cmaes.py) in every compared
 field with np.array_equal, generation after generation, with no state
 copied between them.  mfma: per-shard partial sums; each generation is
-compared at the partial-sum tolerance and the sharded ranks then continue
+compared at the partial-sum tolerance (max norm) and, covariance element by
+element, at the any-order summation bound of its own terms (float_bound: both
+runs carry the error), and the sharded ranks then continue
 from the unsharded state (the two summation orders drift apart by rounding,
 which a run carries forward)."""
 import os
@@ -22,6 +24,23 @@ import torch.distributed as dist
 
 from korali_amd.native import CmaesDevice
 from korali_amd.sharded import ShardedCmaes
+
+
+def float_bound(N, Ysel, w, sigma, C_old, pc, mueff, extra):
+    """The any-order summation bound of every covariance element's own terms
+    (derived in tests/rankmu_ref.py, restated here in plain float64 so that
+    the tool stands alone): 2 (mu+16+extra) 2^-53 (S_de + 2|C_old| + c1|pc_d pc_e|),
+    S_de = (cmu/sigma^2) sum_k w_k |y_kd| |y_ke| inflated by 1.01 for its own
+    rounding; the factor 2 because both compared runs carry the error."""
+    Ysel = np.abs(np.asarray(Ysel, dtype=np.float64).reshape(-1, N))
+    mu = Ysel.shape[0]
+    w = np.abs(np.asarray(w, dtype=np.float64).reshape(mu))
+    ca, cb = N + 1.3, N + 2.0
+    c1 = 2.0 / (ca * ca + mueff)
+    cmu = min(1.0 - c1, 2.0 * (mueff - 2.0 + 1.0 / mueff) / (cb * cb + mueff))
+    S = 1.01 * (cmu / (sigma * sigma)) * ((Ysel * w[:, None]).T @ Ysel)
+    C_old, pc = np.asarray(C_old).reshape(N, N), np.asarray(pc).reshape(N)
+    return 2.0 * (mu + 16 + extra) * 2.0 ** -53 * (S + 2.0 * np.abs(C_old) + c1 * np.abs(np.outer(pc, pc)))
 
 
 def main():
@@ -68,7 +87,17 @@ def main():
             if any(s != states[0] for s in states):
                 print(f"gen {g}: replicated state differs between ranks", flush=True)
                 ok = False
-            ref.generation(g, obj)
+            if cov == "exact":
+                ref.generation(g, obj)
+            else:
+                # the same stages, with the covariance update's inputs kept for the elementwise bound
+                if g == 1:
+                    ref.initialize()
+                ref.synchronize()
+                sigma_old, C_old = ref["Sigma"][0], ref["Covariance Matrix"]
+                ref.sample()
+                ref.evaluate(obj)
+                ref.update(g)
             ref.synchronize()
             X = ref["Sample Population"].reshape(lam, N)
             r0, r1 = sh.r0, sh.r1
@@ -104,6 +133,26 @@ def main():
                     if rel > tol:
                         print(f"gen {g}: {k} rel diff {rel:.3e} > {tol}", flush=True)
                         ok = False
+                # every element within the any-order summation bound of this
+                # generation's terms (tests/rankmu_ref.py); both sides carry the error
+                mu = ref.mu
+                Ysel = X[ref.sorting_index()[:mu].astype(np.int64)] - ref["Previous Mean"]
+                bound = float_bound(N, Ysel, ref["Mu Weights"], sigma_old, C_old, ref["Evolution Path"],
+                                    ref["Effective Mu"][0], extra=world).reshape(-1)
+                err = np.abs(sh.dev["Covariance Matrix"] - ref["Covariance Matrix"])
+                if variant == "diagonal":
+                    off = ~np.eye(N, dtype=bool).reshape(-1)
+                    if not np.array_equal(sh.dev["Covariance Matrix"][off], C_old[off]):
+                        print(f"gen {g}: diagonal covariance: an off-diagonal element changed", flush=True)
+                        ok = False
+                    err, bound = err[~off], bound[~off]
+                worst = float(np.max(err / np.where(bound > 0, bound, 1.0)))
+                print(f"gen {g}: covariance worst err/bound {worst:.4f}", flush=True)
+                if not np.all(err <= bound):
+                    q = int(np.argmax(err - bound))
+                    print(f"gen {g}: Covariance Matrix element {q} off by {err[q]:.3e} > bound {bound[q]:.3e}",
+                          flush=True)
+                    ok = False
                 # teacher-force: continue from the unsharded state on every rank
                 st = {k: ref[k] for k in ("Current Mean", "Covariance Matrix", "Sigma", "Evolution Path",
                                           "Conjugate Evolution Path", "Best Ever Variables", "Best Ever Value")}

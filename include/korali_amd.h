@@ -15,6 +15,7 @@
  *                          univariate/normal/normal.cpp.base:32-35)
  *   kg_cmaes_eval_builtin Optimization::evaluate → user objective
  *                         optimization.cpp.base:26-34, batched over λ
+ *   kg_cmaes_sample_eval  the two above in one call (one launch where it applies)
  *   kg_cmaes_get_candidates / kg_cmaes_set_fitness
  *                         KORALI_START/WAITALL/GET of CMAES::runGeneration
  *                         CMAES.cpp.base:204-224 (host-callback objectives)
@@ -139,6 +140,13 @@ int kg_cmaes_destroy(kg_cmaes_t h);
 int kg_cmaes_initialize(kg_cmaes_t h);
 int kg_cmaes_sample(kg_cmaes_t h);
 int kg_cmaes_eval_builtin(kg_cmaes_t h, int objective);
+/* kg_cmaes_sample + kg_cmaes_eval_builtin in one call, with the same results.
+ * For N <= 128, a full covariance, one shard, infinite bounds and no discrete
+ * variables the draw and the objective are one launch; every other
+ * configuration, and a draw whose overflow guard sends it through the redraw
+ * rounds, runs the two steps.  KORALI_AMD_FUSED_DRAW=0 (read by
+ * kg_cmaes_create) always runs the two steps. */
+int kg_cmaes_sample_eval(kg_cmaes_t h, int objective);
 int kg_cmaes_get_candidates(kg_cmaes_t h, double *X, size_t ld);
 int kg_cmaes_set_fitness(kg_cmaes_t h, const double *F);
 /* Bayesian problems (F(x) = logPosterior, bayesian.cpp.base:79-84): like

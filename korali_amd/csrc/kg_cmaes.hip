@@ -196,25 +196,29 @@ inline unsigned tr_grid(int rows, int N) {
   const int nbm = (rows + BM - 1) / BM, nbn = (N + BN - 1) / BN;
   return (unsigned)(((nbm + TR_XCD - 1) / TR_XCD) * TR_XCD * nbn);
 }
+// The tile's body, shared by k_transform and k_transform_obj: Za / Bt are the
+// caller's LDS (rows padded by 2 doubles: 16-B aligned, so a thread's PR
+// contiguous rows and PC contiguous columns come in 16-B reads: ds_read_b128,
+// 256 B per LDS clock, where the paired ds_read2_b64 moves 128).  Returns
+// false for a surplus workgroup; otherwise i0 is the tile's first row and
+// xo[p][q] the x of row i0 + ty PR + p, column d0 + tx PC + q (0.0 outside
+// the population), and both LDS arrays are free again.
 template <int BM, int BN>
-__global__ void __launch_bounds__(256) k_transform(int N, int rows, int diagonal, const double *__restrict__ Z,
-                                                   const double *__restrict__ B, const double *__restrict__ D,
-                                                   const double *__restrict__ mean, CmaesScalars *__restrict__ sc,
-                                                   const double *__restrict__ lb, const double *__restrict__ ub,
-                                                   double *__restrict__ X, double *__restrict__ BDZ,
-                                                   int *__restrict__ infeas, int no_reserve, int mirrored) {
+__device__ __forceinline__ bool tr_tile(int N, int rows, int diagonal, const double *__restrict__ Z,
+                                        const double *__restrict__ B, const double *__restrict__ D,
+                                        const double *__restrict__ mean, CmaesScalars *__restrict__ sc,
+                                        const double *__restrict__ lb, const double *__restrict__ ub,
+                                        double *__restrict__ X, double *__restrict__ BDZ, int *__restrict__ infeas,
+                                        int no_reserve, int mirrored, double (&Za)[TR_BK][BM + 2],
+                                        double (&Bt)[TR_BK][BN + 2], int &i0, double (&xo)[BM / 8][BN / 32]) {
   constexpr int PR = BM / 8, PC = BN / 32, ZL = BM * TR_BK / 256, BL = BN * TR_BK / 256;
-  // rows padded by 2 doubles: 16-B aligned, so a thread's PR contiguous rows
-  // and PC contiguous columns come in 16-B reads (ds_read_b128: 256 B per
-  // LDS clock, where the paired ds_read2_b64 moves 128)
-  __shared__ __attribute__((aligned(16))) double Za[TR_BK][BM + 2];
-  __shared__ __attribute__((aligned(16))) double Bt[TR_BK][BN + 2];
   const int tid = threadIdx.x;
   const int nbn = (N + BN - 1) / BN;
   const int xcd = blockIdx.x % TR_XCD, j = blockIdx.x / TR_XCD;
   const int rt = (j / nbn) * TR_XCD + xcd, ct = j % nbn;
-  const int i0 = rt * BM, d0 = ct * BN;
-  if (i0 >= rows) return;
+  const int d0 = ct * BN;
+  i0 = rt * BM;
+  if (i0 >= rows) return false;
   const int tx = tid & 31, ty = tid >> 5;
   const double sigma = sc->sigma;
   double acc[PR][PC];
@@ -322,6 +326,8 @@ __global__ void __launch_bounds__(256) k_transform(int N, int rows, int diagonal
   }
 #pragma unroll
   for (int p = 0; p < PR; p++) {
+#pragma unroll
+    for (int q = 0; q < PC; q++) xo[p][q] = 0.0;
     const int i = i0 + ty * PR + p;
     if (i >= rows) continue;
     int bad = 0;
@@ -337,6 +343,7 @@ __global__ void __launch_bounds__(256) k_transform(int N, int rows, int diagonal
       const double bdz = diagonal ? D[d] * zd : acc[p][q];
       const double x = mean[d] + sigma * bdz;
       X[(size_t)i * N + d] = x;
+      xo[p][q] = x;
       if (BDZ) BDZ[(size_t)i * N + d] = bdz;
       if (!isfinite(x) || x < lb[d] || x > ub[d]) bad = 1;
     }
@@ -350,6 +357,21 @@ __global__ void __launch_bounds__(256) k_transform(int N, int rows, int diagonal
         atomicOr(&infeas[i], 1);
     }
   }
+  return true;
+}
+template <int BM, int BN>
+__global__ void __launch_bounds__(256) k_transform(int N, int rows, int diagonal, const double *__restrict__ Z,
+                                                   const double *__restrict__ B, const double *__restrict__ D,
+                                                   const double *__restrict__ mean, CmaesScalars *__restrict__ sc,
+                                                   const double *__restrict__ lb, const double *__restrict__ ub,
+                                                   double *__restrict__ X, double *__restrict__ BDZ,
+                                                   int *__restrict__ infeas, int no_reserve, int mirrored) {
+  __shared__ __attribute__((aligned(16))) double Za[TR_BK][BM + 2];
+  __shared__ __attribute__((aligned(16))) double Bt[TR_BK][BN + 2];
+  int i0;
+  double xo[BM / 8][BN / 32];
+  (void)tr_tile<BM, BN>(N, rows, diagonal, Z, B, D, mean, sc, lb, ub, X, BDZ, infeas, no_reserve, mirrored, Za, Bt, i0,
+                        xo);
 }
 
 // The same transform with the B operand in SCALAR registers (round 4).
@@ -649,6 +671,30 @@ __global__ void __launch_bounds__(256) k_objective(int N, int lam, int obj, cons
   if (!isfinite(f)) atomicOr(&sc->errors, KG_ERR_NONFINITE_F);
 }
 
+// The terms and the final formulas, shared by k_objective2 and
+// k_transform_obj so that their bits cannot drift apart.
+__device__ __forceinline__ double obj_rosenbrock_term(double x, double prev) {
+  const double tt = x - prev * prev;
+  const double uu = 1 - prev;
+  return 100 * (tt * tt) + uu * uu;
+}
+__device__ __forceinline__ double obj_square_term(double x) { return x * x; }
+__device__ __forceinline__ double obj_ackley_cos_term(double x) {
+  const double cc = 2. * 3.141592653589793;
+  return cos_cr(cc * x);
+}
+// r0 / r1: the ordered sums of the first / Ackley's cosine terms
+__device__ __forceinline__ double obj_value(int obj, int N, double r0, double r1) {
+  if (obj == KG_OBJ_NEGATIVE_ROSENBROCK) return -r0;
+  if (obj == KG_OBJ_NEGATIVE_ACKLEY) {
+    const double s1 = r0 / (double)N, s2 = r1 / (double)N;
+    const double e1 = 20. * exp_cr(-0.2 * sqrt(s1));
+    const double e2 = exp_cr(s2);
+    return e1 + e2 - 20. - 2.718281828459045;
+  }
+  return -0.5 * r0;
+}
+
 // The same objectives for N <= 128 with each row's ordered sum split from
 // its terms: the 64 rows' X block is loaded with every load in flight at
 // once; waves 1-3 form the terms of 32-column chunks (Rosenbrock's
@@ -685,7 +731,6 @@ __global__ void __launch_bounds__(256) k_objective2(int N, int lam, int obj, con
   }
   __syncthreads();
   const int nch = (N + OB2_NC - 1) / OB2_NC;
-  const double cc = 2. * 3.141592653589793;
   // producers: terms of chunk ch into buffer ch & 1 (row = lane, columns over waves 1-3)
   auto form = [&](int ch) {
     const int b = ch & 1, d0 = ch * OB2_NC, dn = min(OB2_NC, N - d0);
@@ -707,34 +752,17 @@ __global__ void __launch_bounds__(256) k_objective2(int N, int lam, int obj, con
         if (dd >= dn) break;
         const double x = xs[u];
         if (obj == KG_OBJ_NEGATIVE_ROSENBROCK) {
-          if (d > 0) {
-            const double prev = xp[u];
-            const double tt = x - prev * prev;
-            const double uu = 1 - prev;
-            ta[dd] = 100 * (tt * tt) + uu * uu;
-          }
+          if (d > 0) ta[dd] = obj_rosenbrock_term(x, xp[u]);
         } else {
-          ta[dd] = x * x;
+          ta[dd] = obj_square_term(x);
         }
       }
       return;
     }
-    for (int dd = wid - 1; dd < dn; dd += 3) {
-      const int d = d0 + dd;
-      const double x = xr[d];
-      if (obj == KG_OBJ_NEGATIVE_ROSENBROCK) {
-        if (d > 0) {
-          const double prev = xr[d - 1];
-          const double tt = x - prev * prev;
-          const double u = 1 - prev;
-          ta[dd] = 100 * (tt * tt) + u * u;
-        }
-      } else if (obj == KG_OBJ_NEGATIVE_ACKLEY) {
-        ta[dd] = x * x;
-        tb[dd] = cos_cr(cc * x);
-      } else {
-        ta[dd] = x * x;
-      }
+    for (int dd = wid - 1; dd < dn; dd += 3) {  // (Ackley)
+      const double x = xr[d0 + dd];
+      ta[dd] = obj_square_term(x);
+      tb[dd] = obj_ackley_cos_term(x);
     }
   };
   if (wid > 0) form(0);
@@ -772,16 +800,87 @@ __global__ void __launch_bounds__(256) k_objective2(int N, int lam, int obj, con
   }
   const int i = c0 + lane;
   if (wid != 0 || i >= lam) return;
-  double f;
-  if (obj == KG_OBJ_NEGATIVE_ROSENBROCK)
-    f = -r0;
-  else if (obj == KG_OBJ_NEGATIVE_ACKLEY) {
-    const double s1 = r0 / (double)N, s2 = r1 / (double)N;
-    const double e1 = 20. * exp_cr(-0.2 * sqrt(s1));
-    const double e2 = exp_cr(s2);
-    f = e1 + e2 - 20. - 2.718281828459045;
-  } else
-    f = -0.5 * r0;
+  const double f = obj_value(obj, N, r0, r1);
+  F[i] = f;
+  if (!isfinite(f)) atomicOr(&sc->errors, KG_ERR_NONFINITE_F);
+}
+
+// The draw and the built-in objective in one launch (N <= 128, full
+// covariance, no reserve): k_transform's tile at 16 whole rows x 128 columns,
+// then those rows' objective values.  The x tile stays in LDS (Bt is free
+// after the last K chunk; row stride N + 1 as in k_objective2), every thread
+// forms the terms of its own 2 x 4 outputs, and 16 lanes add them per row in
+// column order: the same ordered chains as k_objective2, one add per term
+// from 0.0, eight terms read per LDS round trip.  A workgroup needs only its
+// own rows, so nothing is handed between workgroups.
+constexpr int TO_BM = 16, TO_BN = 128;
+__global__ void __launch_bounds__(256) k_transform_obj(int N, int rows, const double *__restrict__ Z,
+                                                       const double *__restrict__ B, const double *__restrict__ D,
+                                                       const double *__restrict__ mean, CmaesScalars *__restrict__ sc,
+                                                       const double *__restrict__ lb, const double *__restrict__ ub,
+                                                       double *__restrict__ X, double *__restrict__ BDZ,
+                                                       int *__restrict__ infeas, int mirrored, int obj,
+                                                       double *__restrict__ F, double addEvals) {
+  constexpr int PR = TO_BM / 8, PC = TO_BN / 32;
+  __shared__ __attribute__((aligned(16))) double Za[TR_BK][TO_BM + 2];
+  __shared__ __attribute__((aligned(16))) double Bt[TR_BK][TO_BN + 2];
+  static_assert(2 * TO_BM * (TO_BN + 1) <= TR_BK * (TO_BN + 2), "x tile + one term tile fit in Bt");
+  int i0;
+  double x[PR][PC];
+  if (!tr_tile<TO_BM, TO_BN>(N, rows, 0, Z, B, D, mean, sc, lb, ub, X, BDZ, infeas, 1, mirrored, Za, Bt, i0, x)) return;
+  const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5, ld = N + 1;
+  if (blockIdx.x == 0 && tid == 0) sc->modelEvaluationCount += addEvals;
+  double *Xs = &Bt[0][0];        // [row][d]: x, then Ackley's cosine terms
+  double *Ta = Xs + TO_BM * ld;  // [row][d]: first terms
+  if (obj == KG_OBJ_NEGATIVE_ROSENBROCK) {  // (the only objective that reads a neighbour's x)
+#pragma unroll
+    for (int p = 0; p < PR; p++)
+#pragma unroll
+      for (int q = 0; q < PC; q++) {
+        const int d = tx * PC + q;
+        if (d < N) Xs[(ty * PR + p) * ld + d] = x[p][q];
+      }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int p = 0; p < PR; p++)
+#pragma unroll
+    for (int q = 0; q < PC; q++) {
+      const int r = ty * PR + p, d = tx * PC + q;
+      if (d >= N) continue;
+      if (obj == KG_OBJ_NEGATIVE_ROSENBROCK) {
+        if (d > 0) Ta[r * ld + d] = obj_rosenbrock_term(x[p][q], Xs[r * ld + d - 1]);
+      } else {
+        Ta[r * ld + d] = obj_square_term(x[p][q]);
+        if (obj == KG_OBJ_NEGATIVE_ACKLEY) Xs[r * ld + d] = obj_ackley_cos_term(x[p][q]);
+      }
+    }
+  __syncthreads();
+  const int i = i0 + tid;
+  if (tid >= TO_BM || i >= rows) return;
+  const double *ta = Ta + tid * ld, *tb = Xs + tid * ld;
+  double r0 = 0.0, r1 = 0.0;
+  int d = obj == KG_OBJ_NEGATIVE_ROSENBROCK ? 1 : 0;
+  if (obj == KG_OBJ_NEGATIVE_ACKLEY) {
+    for (; d + 8 <= N; d += 8) {
+      double t[8], c[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) t[u] = ta[d + u], c[u] = tb[d + u];
+#pragma unroll
+      for (int u = 0; u < 8; u++) r0 += t[u], r1 += c[u];
+    }
+    for (; d < N; d++) r0 += ta[d], r1 += tb[d];
+  } else {
+    for (; d + 8 <= N; d += 8) {
+      double t[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) t[u] = ta[d + u];
+#pragma unroll
+      for (int u = 0; u < 8; u++) r0 += t[u];
+    }
+    for (; d < N; d++) r0 += ta[d];
+  }
+  const double f = obj_value(obj, N, r0, r1);
   F[i] = f;
   if (!isfinite(f)) atomicOr(&sc->errors, KG_ERR_NONFINITE_F);
 }
@@ -3217,6 +3316,9 @@ struct kg_cmaes_s {
   // KORALI_AMD_FUSED_SELECT=0 / KORALI_AMD_EARLY_PUBLISH=0 (A/B, read when the
   // handle is created): the separate selection kernels / publish after sigma
   bool fusedSel = true, earlyPub = true;
+  // KORALI_AMD_FUSED_DRAW=0 (A/B, read likewise): the separate transform and
+  // objective kernels
+  bool fusedDraw = true;
   unsigned *meanArrived = nullptr;  // k_mean3<true>'s arrival counter (zero from create's fill, then monotonic)
   unsigned meanTarget = 0;          // its value once the launch enqueued last has arrived
   MtStream normal, uniform;
@@ -3666,6 +3768,8 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
     h->fusedSel = !(e && *e == '0');
     e = getenv("KORALI_AMD_EARLY_PUBLISH");
     h->earlyPub = !(e && *e == '0');
+    e = getenv("KORALI_AMD_FUSED_DRAW");
+    h->fusedDraw = !(e && *e == '0');
   }
   if (set_current(h, h->lamCfg, h->muCfg)) return 1;
   KG_HIP(hipMemcpy(h->lb, lb.data(), N * sizeof(double), hipMemcpyHostToDevice));
@@ -3964,11 +4068,31 @@ static int cmaes_resample(kg_cmaes_t h) {
 
 static bool plain_update(kg_cmaes_t h);  // (with kg_cmaes_update)
 
-int kg_cmaes_sample(kg_cmaes_t h) {
+// the draw and the built-in objective in one launch (k_transform_obj): N <=
+// 128, full covariance, one shard, no reserve (all bounds infinite, no
+// discrete variables), the LDS-tiled transform
+static bool fused_draw(kg_cmaes_t h, int objective) {
+  return h->fusedDraw && objective >= 0 && objective <= 2 && h->N <= TO_BN && !h->cfg.diagonal_covariance &&
+         h->shards == 1 && h->R == 0 && !h->finiteBounds && !h->hasDiscrete && h->nc == 0 && h->trW == 0;
+}
+static int cmaes_transform_obj(kg_cmaes_t h, int objective) {
+  Stage st(h, "transform");
+  hipLaunchKernelGGL(k_transform_obj, dim3(tr_grid<TO_BM, TO_BN>(h->lam, h->N)), dim3(256), 0, h->stream, h->N, h->lam,
+                     h->Z, h->B, h->D, h->mean, h->sc, h->lb, h->ub, h->X, h->BDZ, h->infeas, h->mirrored ? 1 : 0,
+                     objective, h->F, (double)h->lam);
+  KG_HIP(hipGetLastError());
+  return 0;
+}
+
+// kg_cmaes_sample (objective < 0) and kg_cmaes_sample_eval's first step;
+// *evaluated: F already holds the objective's values (the fused launch ran)
+static int cmaes_sample(kg_cmaes_t h, int objective, bool *evaluated) {
   const int N = h->N;
+  *evaluated = false;
   if (flush_consume(h)) return 1;  // (a draw whose update never came)
   if (!h->sampleBegun && cmaes_draw_begin(h)) return 1;
   h->sampleBegun = false;
+  const bool fused = fused_draw(h, objective);
   if (cmaes_eigen(h)) return 1;
   {
     Stage st(h, "rng_polar");  // what of the producer + polar pass the eigensolver did not hide
@@ -3985,8 +4109,11 @@ int kg_cmaes_sample(kg_cmaes_t h) {
       redraw = true;
     }
   }
-  if (redraw) return cmaes_resample(h);
-  {
+  if (redraw) return cmaes_resample(h);  // (the caller evaluates separately)
+  if (fused) {
+    if (cmaes_transform_obj(h, objective)) return 1;
+    *evaluated = true;
+  } else {
     Stage st(h, "transform");
     // no redraw possible: the population is the first lambda blocks; a shard
     // transforms its own rows only
@@ -4005,6 +4132,18 @@ int kg_cmaes_sample(kg_cmaes_t h) {
   h->consumePending = true;
   if (!plain_update(h)) return flush_consume(h);
   return 0;
+}
+
+int kg_cmaes_sample(kg_cmaes_t h) {
+  bool evaluated = false;
+  return cmaes_sample(h, -1, &evaluated);
+}
+
+int kg_cmaes_sample_eval(kg_cmaes_t h, int objective) {
+  KG_CHECK(objective >= 0 && objective <= 2, "unknown builtin objective");
+  bool evaluated = false;
+  if (cmaes_sample(h, objective, &evaluated)) return 1;
+  return evaluated ? 0 : kg_cmaes_eval_builtin(h, objective);
 }
 
 int kg_cmaes_eval_builtin(kg_cmaes_t h, int objective) {
@@ -4631,8 +4770,7 @@ int kg_cmaes_update_finalize(kg_cmaes_t h, size_t generation) {
 int kg_cmaes_generation(kg_cmaes_t h, size_t generation, int objective) {
   KG_CHECK(h->shards == 1, "a population-sharded generation needs the caller's collectives between its stages");
   if (generation == 1 && kg_cmaes_initialize(h)) return 1;
-  if (kg_cmaes_sample(h)) return 1;
-  if (kg_cmaes_eval_builtin(h, objective)) return 1;
+  if (kg_cmaes_sample_eval(h, objective)) return 1;
   return kg_cmaes_update(h, generation);
 }
 

@@ -1134,11 +1134,13 @@ struct CmaesModule : SolverModule {
       check(kg_cmaes_population_size(h, &cur, nullptr));
       lam = cur;
       r1 = lam;
+    } else if (objective >= 0 && !dist) {
+      check(kg_cmaes_sample_eval(h, objective));  // (the draw and the objective in one launch where it applies)
     } else {
       check(kg_cmaes_sample(h));
     }
     if (objective >= 0) {
-      check(kg_cmaes_eval_builtin(h, objective));
+      if (!constraintFns.empty() || dist) check(kg_cmaes_eval_builtin(h, objective));
     } else if (replicated) {
       splitEvaluate(gen);
     } else if (dist) {

@@ -98,6 +98,7 @@ DEA_ACCEPT_RULES = {"best": 0, "greedy": 1, "iterative": 2, "improved": 3}
 EXPORTED = [
     "kg_last_error", "kg_abi_version", "kg_device_count",
     "kg_cmaes_create", "kg_cmaes_destroy", "kg_cmaes_initialize", "kg_cmaes_sample", "kg_cmaes_eval_builtin",
+    "kg_cmaes_sample_eval",
     "kg_cmaes_get_candidates", "kg_cmaes_set_fitness", "kg_cmaes_set_log_posterior", "kg_cmaes_update", "kg_cmaes_generation",
     "kg_cmaes_begin_sample", "kg_cmaes_wait_termination_fields", "kg_cmaes_set_gradients", "kg_cmaes_update_partial", "kg_cmaes_update_finalize",
     "kg_cmaes_shard_row_count", "kg_cmaes_update_rows",
@@ -143,6 +144,7 @@ def lib():
                   "kg_cmaes_begin_sample"):
             getattr(L, f).argtypes = [vp]
         L.kg_cmaes_eval_builtin.argtypes = [vp, ip]
+        L.kg_cmaes_sample_eval.argtypes = [vp, ip]
         L.kg_cmaes_get_candidates.argtypes = [vp, dp, sz]
         L.kg_cmaes_set_fitness.argtypes = [vp, dp]
         L.kg_cmaes_set_log_posterior.argtypes = [vp, dp]
@@ -342,6 +344,11 @@ class CmaesDevice:
     def evaluate(self, objective):
         check(self._L.kg_cmaes_eval_builtin(self.h, OBJECTIVES[objective.lower()] if isinstance(objective, str)
                                             else int(objective)))
+
+    def sample_eval(self, objective):
+        """sample() + evaluate(objective) in one call (kg_cmaes_sample_eval)."""
+        check(self._L.kg_cmaes_sample_eval(self.h, OBJECTIVES[objective.lower()] if isinstance(objective, str)
+                                           else int(objective)))
 
     def update(self, generation):
         check(self._L.kg_cmaes_update(self.h, int(generation)))

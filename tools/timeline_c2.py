@@ -4,7 +4,7 @@ kernel of a generation's update), each with its start offset from the
 generation's start, its duration and the idle gap on the GPU before it.
 
 Per generation it also prints the update tail: from the start of k_transform
-to the end of the last kernel before k_sigma, and to the end of the kernel
+(or k_transform_obj, the draw with the objective folded in) to the end of the last kernel before k_sigma, and to the end of the kernel
 that hands C to the host (k_publish_c).
 
     python tools/timeline_c2.py <dir with *kernel_trace.csv> [generations]
@@ -49,7 +49,7 @@ def main():
             prev_end = max(prev_end, e)
         print(f"    GPU busy {busy / 1e3:.1f} us")
         gen = rows[a:b]
-        tr = [r for r in gen if base(r[2]).endswith(("k_transform", "k_transform_sc"))]
+        tr = [r for r in gen if base(r[2]).endswith(("k_transform", "k_transform_sc", "k_transform_obj"))]
         if tr and len(gen) > 1:
             pub = [r for r in gen if base(r[2]).endswith("k_publish_c")]
             line = f"    tail (k_transform start -> end of the last kernel before k_sigma): {(gen[-2][1] - tr[-1][0]) / 1e3:.1f} us"

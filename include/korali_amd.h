@@ -241,7 +241,9 @@ int kg_cmaes_device_ptr(kg_cmaes_t h, const char *name, void **ptr);
 int kg_cmaes_stream(kg_cmaes_t h, void **stream);
 /* kernel timing probe: average device time (ms) of the named kernel family
  * over the last generation(s) since the previous call, measured with HIP
- * events on the handle's stream; enable with kg_cmaes_profile(h, 1). */
+ * events on the handle's stream; enable with kg_cmaes_profile(h, 1).
+ * "adaptC_row" / "adaptC_lane" carry no time: their count is how often that
+ * exact covariance kernel was launched. */
 int kg_cmaes_profile(kg_cmaes_t h, int enable);
 int kg_cmaes_profile_read(kg_cmaes_t h, const char *stage, double *ms_total, size_t *count);
 /* A stage bracketed by the caller (phase 0 = begin, 1 = end): an event pair

@@ -1250,8 +1250,8 @@ __global__ void __launch_bounds__(256) k_gather_selected(int N, int mu, const do
   const int i = blockIdx.x;
   const size_t src = (size_t)idx[i] * N;
   for (int d = threadIdx.x; d < N; d += blockDim.x) Y[(size_t)i * N + d] = X[src + d];
-  // m_prev (updateDistribution :603): read by k_mean and, concurrently, by
-  // the rank-mu sum on the second stream
+  // m_prev (updateDistribution :603): read by the mean kernel and,
+  // concurrently, by the rank-mu sum on the second stream
   if (i == 0)
     for (int d = threadIdx.x; d < N; d += blockDim.x) prevMean[d] = mean[d];
 }
@@ -1263,7 +1263,8 @@ __global__ void __launch_bounds__(256) k_gather_selected(int N, int mu, const do
 // = fl(fl(T_kd * Yc_ke) / s2)  with  Yc_kd = fl(x_kd - m_d),
 //   T_kd = fl(fl(ccovmu w_k) Yc_kd),  s2 = fl(sigma sigma).
 // k_rankmu_prep forms Yc (k-major, the e side) and T (transposed, d-major,
-// the d side) once; k_adaptC_exact2 then spends per term one product, the
+// the d side) once; the covariance kernels (k_adaptC_row, k_adaptC_lane)
+// then spend per term one product, the
 // Markstein-corrected quotient  q0 = p y, r = fma(-q0, s2, p),
 // q = fma(r, y, q0)  (y = fl(1/s2); q == fl(p / s2) exactly whenever p and
 // s2 stay far from underflow / overflow, Markstein's theorem) and the
@@ -1515,290 +1516,6 @@ __global__ void __launch_bounds__(256) k_rank_select(int lam, int N, int mu, uns
       currBestVars[d] = v;
       if (fl) bestEverVars[d] = v;
     }
-  }
-}
-
-// one wave per row d (4 rows per workgroup), one lane per column e (64
-// columns per workgroup).  Per chunk of AX_K k: the workgroup stages the
-// Yc rows of its 64 columns and the T values of its 4 rows in LDS (the next
-// chunk's global loads are in flight while the current chunk is summed);
-// each lane then runs its ordered chain reading Yc[k][lane] and the
-// wave-uniform T[k][d] (broadcast) from LDS.
-constexpr int AX_K = 64, AX_B = 16;
-template <bool kMarkstein>
-__device__ __forceinline__ double rankmu_term(double c, double t, double yc, double s2, double y) {
-  const double p = t * yc;
-  double q;
-  if (kMarkstein) {
-    const double q0 = p * y;
-    const double r = __builtin_fma(-q0, s2, p);
-    q = __builtin_fma(r, y, q0);
-  } else {
-    q = p / s2;
-  }
-  return c + q;
-}
-template <bool kMarkstein>
-__device__ __forceinline__ double rankmu_quot(double t, double yc, double s2, double y) {
-  const double p = t * yc;
-  if (kMarkstein) {
-    const double q0 = p * y;
-    const double r = __builtin_fma(-q0, s2, p);
-    return __builtin_fma(r, y, q0);
-  }
-  return p / s2;
-}
-template <bool kMarkstein>
-__device__ __forceinline__ double rankmu_chunk(double c, const double *__restrict__ ys, const double *__restrict__ ts,
-                                               int cnt, double s2, double y) {
-  if (cnt == AX_K) {
-    // operands of the next 16 terms are read from LDS while the current 16
-    // quotients (independent) are formed and added in order
-    double ya[AX_B], ta[AX_B], yb[AX_B], tb[AX_B];
-#pragma unroll
-    for (int u = 0; u < AX_B; u++) {
-      ya[u] = ys[u * 64];
-      ta[u] = ts[u];
-    }
-#pragma unroll
-    for (int j = 0; j < AX_K / AX_B; j += 2) {
-#pragma unroll
-      for (int u = 0; u < AX_B; u++) {
-        yb[u] = ys[((j + 1) * AX_B + u) * 64];
-        tb[u] = ts[(j + 1) * AX_B + u];
-      }
-      double q[AX_B];
-#pragma unroll
-      for (int u = 0; u < AX_B; u++) q[u] = rankmu_quot<kMarkstein>(ta[u], ya[u], s2, y);
-#pragma unroll
-      for (int u = 0; u < AX_B; u++) c += q[u];
-      if (j + 2 < AX_K / AX_B) {
-#pragma unroll
-        for (int u = 0; u < AX_B; u++) {
-          ya[u] = ys[((j + 2) * AX_B + u) * 64];
-          ta[u] = ts[(j + 2) * AX_B + u];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < AX_B; u++) q[u] = rankmu_quot<kMarkstein>(tb[u], yb[u], s2, y);
-#pragma unroll
-      for (int u = 0; u < AX_B; u++) c += q[u];
-    }
-  } else {
-    for (int u = 0; u < cnt; u++) c = rankmu_term<kMarkstein>(c, ts[u], ys[u * 64], s2, y);
-  }
-  return c;
-}
-template <bool kMarkstein>
-__device__ __forceinline__ double rankmu_rows(double c, const double *__restrict__ Yc, const double *__restrict__ Tt,
-                                              int N, int mu, int d0, int e0, int wid, int lane, double s2, double y,
-                                              double (*Ys)[AX_K][64], double (*Ts)[4][AX_K]) {
-  const int tid = threadIdx.x;
-  // staging: thread t loads Yc[k0 + t/16 + 16 j][e0 + 4 (t%16) .. +3] for
-  // j < 4 (16-B vector loads), and T[d0 + t/64][k0 + t%64]
-  const int kr = tid >> 4, ec = (tid & 15) * 4;
-  double2 yv[4][2];
-  double tv = 0.0;
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int k = k0 + kr + 16 * j;
-      const double *src = Yc + (size_t)(k < mu ? k : mu - 1) * N + e0 + ec;  // clamped rows are never summed
-      if ((N & 1) == 0 && e0 + ec + 3 < N) {  // 16-B aligned rows
-        yv[j][0] = *(const double2 *)src;
-        yv[j][1] = *(const double2 *)(src + 2);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) ((double *)&yv[j][0])[q] = (e0 + ec + q < N) ? src[q] : 0.0;
-      }
-    }
-    const int dr = d0 + (tid >> 6), kk = k0 + (tid & 63);
-    tv = (dr < N && kk < mu) ? Tt[(size_t)dr * mu + kk] : 0.0;
-  };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      double *dst = &Ys[buf][kr + 16 * j][ec];
-      *(double2 *)dst = yv[j][0];
-      *(double2 *)(dst + 2) = yv[j][1];
-    }
-    Ts[buf][tid >> 6][tid & 63] = tv;
-  };
-  load(0);
-  store(0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = 0; k0 < mu; k0 += AX_K) {
-    const bool more = k0 + AX_K < mu;
-    if (more) load(k0 + AX_K);  // in flight during the chunk below
-    c = rankmu_chunk<kMarkstein>(c, &Ys[buf][0][lane], &Ts[buf][wid][0], min(AX_K, mu - k0), s2, y);
-    if (more) store(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-  return c;
-}
-
-__global__ void __launch_bounds__(256) k_adaptC_exact2(int N, int mu, int diagonal, const double *__restrict__ Yc,
-                                                       const double *__restrict__ Tt,
-                                                       const double *__restrict__ pc, double *C,
-                                                       const CmaesScalars *__restrict__ sc) {
-  __shared__ __attribute__((aligned(16))) double Ys[2][AX_K][64];
-  __shared__ double Ts[2][4][AX_K];
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int d0 = blockIdx.x * 4, e0 = blockIdx.y * 64;
-  if (e0 > d0 + 3) return;  // workgroup-uniform: entirely above the diagonal
-  const int d = d0 + wid, e = e0 + lane;
-  const bool active = d < N && e < N && e <= d && (!diagonal || e == d);
-  const double ccov1 = sc->ccov1, ccovmu = sc->ccovmu, cc = sc->cumulativeCovariance;
-  const int hsig = (int)sc->hsig;
-  const double s2 = sc->sigma * sc->sigma;
-  double c = 0.0;
-  if (active) {
-    const double Cde = C[(size_t)d * N + e];
-    c = (1 - ccov1 - ccovmu) * Cde + ccov1 * (pc[d] * pc[e] + (1 - hsig) * cc * (2. - cc) * Cde);
-  }
-  const int ex = (int)((__double_as_longlong(s2) >> 52) & 0x7ff) - 1023;
-  if (__builtin_amdgcn_readfirstlane((int)(sc->rmuOutOfRange == 0u && ex >= -100 && ex <= 100)))
-    c = rankmu_rows<true>(c, Yc, Tt, N, mu, d0, e0, wid, lane, s2, 1.0 / s2, Ys, Ts);
-  else
-    c = rankmu_rows<false>(c, Yc, Tt, N, mu, d0, e0, wid, lane, s2, 0.0, Ys, Ts);
-  if (active) {
-    C[(size_t)d * N + e] = c;
-    if (e < d) C[(size_t)e * N + d] = c;
-  }
-}
-
-// The same ordered sums with the chain split from its operands.  One
-// workgroup per 4-row x 16-column tile of the lower triangle: wave 0 runs the
-// 64 chains (one per lane, kc_add over quotients staged in LDS, one dependent
-// add per term), waves 1..AX3_P form the next 64 quotients of every chain
-// (Yc / T loads one chunk ahead, the Markstein quotient) meanwhile.  A single
-// wave forming its own quotients issues five FP64 operations per term and is
-// issue-bound well above the add latency; here the add chain is the bound.
-// Tiles of 16-column block cb run on XCD cb % 8 (workgroup slot s -> XCD s % 8),
-// so a column block of Yc is fetched from HBM into one L2.
-// A workgroup barrier that orders LDS only: __syncthreads' release fence
-// waits for every outstanding global load too (s_waitcnt vmcnt(0)), which
-// would expose the prefetches issued for later chunks at every round
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n s_barrier" ::: "memory"); }
-// row stride 73: odd (two-way bank pairs at most for the consumer's per-lane
-// rows) and >= 70, so every producer slot p + 7 u (u < 10) stores without a
-// branch (slots 64..69 are never summed)
-constexpr int AX3_P = 7, AX3_K = 64, AX3_S = 73;  // producers, chunk, LDS row stride
-__device__ __forceinline__ int ax3_tiles_in(int N, int cb) {  // row blocks of column block cb
-  const int R = (N + 3) / 4, lo = 4 * cb;
-  return R > lo ? R - lo : 0;
-}
-int ax3_slots(int N) {
-  int mx = 0;
-  for (int x = 0; x < 8; x++) {
-    int cnt = 0;
-    for (int cb = x; 16 * cb < N; cb += 8) cnt += std::max(0, (N + 3) / 4 - 4 * cb);
-    mx = std::max(mx, cnt);
-  }
-  return 8 * mx;
-}
-template <bool kMarkstein>
-__device__ __forceinline__ double ax3_run(double c, const double *__restrict__ Yc, const double *__restrict__ Tt,
-                                          int N, int mu, int d0, int e0, int wid, int lane, double s2, double y,
-                                          double (*Q)[64 * AX3_S + 16]) {
-  const int r = lane >> 4, cc = lane & 15, d = d0 + r, e = e0 + cc;
-  const bool rowok = d < N, colok = e < N;
-  constexpr int KP = (AX3_K + AX3_P - 1) / AX3_P;  // quotients per producer lane per chunk
-  double yA[KP], tA[KP], yB[KP], tB[KP];
-  const int p = wid - 1;
-  auto load = [&](int k0, double(&yv)[KP], double(&tv)[KP]) {
-#pragma unroll
-    for (int u = 0; u < KP; u++) {
-      const int kl = p + AX3_P * u, k = k0 + kl;
-      const bool ok = kl < AX3_K && k < mu;
-      yv[u] = (ok && colok) ? Yc[(size_t)k * N + e] : 0.0;
-      tv[u] = (ok && rowok) ? Tt[(size_t)d * mu + k] : 0.0;
-    }
-  };
-  auto store = [&](int buf, const double(&yv)[KP], const double(&tv)[KP]) {
-#pragma unroll
-    for (int u = 0; u < KP; u++) {
-      const int kl = p + AX3_P * u;
-      Q[buf][lane * AX3_S + kl] = rankmu_quot<kMarkstein>(tv[u], yv[u], s2, y);
-    }
-  };
-  auto chain = [&](int k0, int buf) {
-    const int cnt = min(AX3_K, mu - k0), g = cnt >> 4;
-    const double *row = &Q[buf][lane * AX3_S];
-    c = chains::kc_add(c, lds_addr(row), __builtin_amdgcn_readfirstlane((unsigned)g));
-    for (int u = 16 * g; u < cnt; u++) c += row[u];
-  };
-  // producers: in the round where wave 0 sums chunk k, the loads of chunk
-  // k+2 are issued first, then chunk k+1's quotients are formed from the
-  // registers its loads filled one round earlier (two register sets in
-  // turn).  Producer and consumer waves run separate loops with the same
-  // barrier count, so the compiler keeps each register set in place.
-  if (wid > 0) {
-    load(0, yA, tA);
-    load(AX3_K, yB, tB);
-    store(0, yA, tA);
-    lds_barrier();
-    for (int k0 = 0; k0 < mu; k0 += 2 * AX3_K) {
-      load(k0 + 2 * AX3_K, yA, tA);  // (rows past mu load zeros)
-      if (k0 + AX3_K < mu) store(1, yB, tB);
-      lds_barrier();
-      if (k0 + AX3_K >= mu) break;
-      load(k0 + 3 * AX3_K, yB, tB);
-      if (k0 + 2 * AX3_K < mu) store(0, yA, tA);
-      lds_barrier();
-    }
-  } else {
-    lds_barrier();
-    for (int k0 = 0; k0 < mu; k0 += 2 * AX3_K) {
-      chain(k0, 0);
-      lds_barrier();
-      if (k0 + AX3_K >= mu) break;
-      chain(k0 + AX3_K, 1);
-      lds_barrier();
-    }
-  }
-  return c;
-}
-__global__ void __launch_bounds__(64 * (AX3_P + 1)) k_adaptC_exact3(int N, int mu, int diagonal,
-                                                                    const double *__restrict__ Yc,
-                                                                    const double *__restrict__ Tt,
-                                                                    const double *__restrict__ pc, double *C,
-                                                                    const CmaesScalars *__restrict__ sc) {
-  __shared__ __attribute__((aligned(16))) double Q[2][64 * AX3_S + 16];
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-  // slot -> (column block, row block)
-  const int x = blockIdx.x & 7;
-  int j = blockIdx.x >> 3, cb = x, rb = -1;
-  for (; 16 * cb < N; cb += 8) {
-    const int t = ax3_tiles_in(N, cb);
-    if (j < t) {
-      rb = 4 * cb + j;
-      break;
-    }
-    j -= t;
-  }
-  if (rb < 0) return;  // workgroup-uniform: past this XCD's tiles
-  const int d0 = 4 * rb, e0 = 16 * cb;
-  const int d = d0 + (lane >> 4), e = e0 + (lane & 15);
-  const bool active = wid == 0 && d < N && e < N && e <= d && (!diagonal || e == d);
-  const double ccov1 = sc->ccov1, ccovmu = sc->ccovmu, cc = sc->cumulativeCovariance;
-  const int hsig = (int)sc->hsig;
-  const double s2 = sc->sigma * sc->sigma;
-  double c = 0.0;
-  if (active) {
-    const double Cde = C[(size_t)d * N + e];
-    c = (1 - ccov1 - ccovmu) * Cde + ccov1 * (pc[d] * pc[e] + (1 - hsig) * cc * (2. - cc) * Cde);
-  }
-  const int ex = (int)((__double_as_longlong(s2) >> 52) & 0x7ff) - 1023;
-  if (__builtin_amdgcn_readfirstlane((int)(sc->rmuOutOfRange == 0u && ex >= -100 && ex <= 100)))
-    c = ax3_run<true>(c, Yc, Tt, N, mu, d0, e0, wid, lane, s2, 1.0 / s2, Q);
-  else
-    c = ax3_run<false>(c, Yc, Tt, N, mu, d0, e0, wid, lane, s2, 0.0, Q);
-  if (active) {
-    C[(size_t)d * N + e] = c;
-    if (e < d) C[(size_t)e * N + d] = c;
   }
 }
 
@@ -2083,13 +1800,7 @@ __global__ void __launch_bounds__(256) k_adaptC_lane(int N, int mu, int diagonal
     al_run<false>(N, mu, diagonal, Yc, Tt, pc, C, sc, tbase, pack, Ts, Ys);
 }
 
-// mean :603-609 and mean update :623-624.  The sum over the μ selected rows
-// is sequential per d (the reference's order); a workgroup owns MN_D columns:
-// all its threads stream the products w_i Y[i][d] into LDS, 256 rows at a
-// time (next chunk loaded while the current one is summed), and MN_D lanes
-// of wave 0 add them in order (an add-only chain at the FP64 add latency).
-constexpr int MN_D = 8, MN_R = 256;
-// the gradient-informed mean step (CMAES.cpp.base:611-621), after k_mean:
+// the gradient-informed mean step (CMAES.cpp.base:611-621), after the mean:
 // mean_d += ((w_i step) / sqrt(N)) g_(i),d in selection order, then the
 // mean update again
 __global__ void k_mean_gradient(int N, int mu, double step, const double *__restrict__ G,
@@ -2105,117 +1816,10 @@ __global__ void k_mean_gradient(int N, int mu, double step, const double *__rest
   meanUpdate[d] = (acc - prevMean[d]) / sc->sigma;
 }
 
-__global__ void __launch_bounds__(256) k_mean(int N, int mu, const double *__restrict__ Y,
-                                              const double *__restrict__ w, double *mean, double *prevMean,
-                                              double *meanUpdate, const CmaesScalars *__restrict__ sc) {
-  __shared__ double buf[2][MN_R][MN_D + 1];
-  const int tid = threadIdx.x;
-  const int d0 = blockIdx.x * MN_D;
-  const int nd = (N - d0) < MN_D ? (N - d0) : MN_D;
-  const int nchunks = (mu + MN_R - 1) / MN_R;
-  double v[8];
-  auto fetch = [&](int chunk) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int e = tid + 256 * u, r = e >> 3, c = e & 7, i = chunk * MN_R + r;
-      v[u] = (i < mu && c < nd) ? w[i] * Y[(size_t)i * N + d0 + c] : 0.0;
-    }
-  };
-  auto put = [&](int b) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int e = tid + 256 * u;
-      buf[b][e >> 3][e & 7] = v[u];
-    }
-  };
-  fetch(0);
-  put(0);
-  __syncthreads();
-  double acc = 0.;
-  for (int ch = 0; ch < nchunks; ch++) {
-    if (ch + 1 < nchunks) fetch(ch + 1);
-    if (tid < nd) {
-      const int rn = (mu - ch * MN_R) < MN_R ? (mu - ch * MN_R) : MN_R;
-      const double(*bb)[MN_D + 1] = buf[ch & 1];
-      int r = 0;
-      for (; r + 8 <= rn; r += 8) {
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) t[u] = bb[r + u][tid];
-#pragma unroll
-        for (int u = 0; u < 8; u++) acc += t[u];
-      }
-      for (; r < rn; r++) acc += bb[r][tid];
-    }
-    if (ch + 1 < nchunks) put((ch + 1) & 1);
-    __syncthreads();
-  }
-  if (tid < nd) {
-    const int d = d0 + tid;
-    const double prev = prevMean[d];  // copied by k_gather_selected
-    mean[d] = acc;
-    meanUpdate[d] = (acc - prev) / sc->sigma;
-  }
-}
-
-// k_mean on the chain primitive: lane c of wave 0 adds w_i y_(i),d0+c in
-// selection order (kc_add: ~15 cycles per product); waves 1-3 stage the next
-// MN2_R products of the 8 dimensions into the other half of a double-buffered
-// LDS ring (transposed: dimension-major, zero past mu) while the chain runs.
-constexpr int MN2_R = 1024, MN2_RS = MN2_R + 32;  // rows per chunk; row stride (the chain reads up to 31 ahead)
-size_t mean2_lds_bytes() { return 2 * (size_t)MN_D * MN2_RS * sizeof(double); }
-__global__ void __launch_bounds__(256) k_mean2(int N, int mu, const double *__restrict__ Y,
-                                               const double *__restrict__ w, double *mean, double *prevMean,
-                                               double *meanUpdate, const CmaesScalars *__restrict__ sc) {
-  extern __shared__ __attribute__((aligned(16))) double pbuf[];  // [2][MN_D][MN2_RS]
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int d0 = blockIdx.x * MN_D;
-  const int nd = (N - d0) < MN_D ? (N - d0) : MN_D;
-  const int nchunks = (mu + MN2_R - 1) / MN2_R;
-  // eight products' loads in flight per thread (one at a time, each round
-  // trip to L2/HBM would be exposed: the staging, not the chain, was the bound)
-  auto stage = [&](int chunk, int t0, int nt) {
-    double *b = pbuf + (size_t)(chunk & 1) * MN_D * MN2_RS;
-    for (int e0 = t0; e0 < MN_D * MN2_R; e0 += 8 * nt) {
-      double wv[8], yv[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const int e = e0 + u * nt, r = e >> 3, c = e & 7, i = chunk * MN2_R + r;
-        const bool ok = e < MN_D * MN2_R && i < mu && c < nd;
-        wv[u] = ok ? w[i] : 0.0;
-        yv[u] = ok ? Y[(size_t)i * N + d0 + c] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const int e = e0 + u * nt, r = e >> 3, c = e & 7;
-        if (e < MN_D * MN2_R) b[(size_t)c * MN2_RS + r] = wv[u] * yv[u];
-      }
-    }
-  };
-  stage(0, tid, 256);
-  __syncthreads();
-  double acc = 0.0;
-  const int c = lane < nd ? lane : 0;
-  for (int ch = 0; ch < nchunks; ch++) {
-    if (wid == 0) {
-      const int rn = min(MN2_R, mu - ch * MN2_R);
-      const double *b = pbuf + (size_t)(ch & 1) * MN_D * MN2_RS + (size_t)c * MN2_RS;
-      acc = chains::kc_add(acc, lds_addr(b), __builtin_amdgcn_readfirstlane((unsigned)(rn + 15) >> 4));
-    } else if (ch + 1 < nchunks) {
-      stage(ch + 1, tid - 64, 192);
-    }
-    __syncthreads();
-  }
-  if (wid == 0 && lane < nd) {
-    const int d = d0 + lane;
-    const double prev = prevMean[d];  // copied by k_gather_selected
-    mean[d] = acc;
-    meanUpdate[d] = (acc - prev) / sc->sigma;
-  }
-}
-
-// k_mean on ROW chains (round 4): every 16-lane row of a wave owns one
-// dimension d and runs its ordered chain mean_d = sum_i w_i y_(i),d with
+// mean :603-609 and mean update :623-624.  The sum over the μ selected rows
+// is sequential per d (the reference's order), on ROW chains: every 16-lane
+// row of a wave owns one dimension d and runs its ordered chain
+// mean_d = sum_i w_i y_(i),d with
 // kc_row16 (one v_fmac_f64 DPP broadcast per element: lane j of the row holds
 // the product of element 16 g + j); four chains per wave, sixteen per
 // workgroup.  The selected rows are staged through LDS in chunks of MR_K
@@ -2451,87 +2055,6 @@ __global__ void __launch_bounds__(PR_T) k_paths3(int N, unsigned long long gen, 
                                                  double *auxBDZ, double *ps, double *pc, CmaesScalars *sc) {
   paths3_body<false>(N, gen, B, D, meanUpdate, auxBDZ, ps, pc, sc, nullptr, 0u);
 }
-
-// evolution paths for N <= 128 (full covariance): B staged once in LDS (row
-// stride 129: column and row walks both conflict-free), the two ordered
-// matrix-vector chains and the |p_sigma| chain on the chain primitives.
-constexpr int PA2_LD = 129;
-// (the vectors start 16-byte aligned: kc_lock_asc reads w in pairs)
-__host__ __device__ inline size_t paths2_vec(int N) { return ((size_t)N + 33) & ~(size_t)1; }
-__host__ __device__ inline size_t paths2_bs(int N) { return ((size_t)(N + 16) * PA2_LD + 1) & ~(size_t)1; }
-size_t paths2_lds_bytes(int N) { return (paths2_bs(N) + 3 * paths2_vec(N)) * sizeof(double); }
-__global__ void __launch_bounds__(256) k_paths2(int N, unsigned long long gen, const double *__restrict__ B,
-                                                const double *__restrict__ D, const double *__restrict__ meanUpdate,
-                                                double *auxBDZ, double *ps, double *pc, CmaesScalars *sc) {
-  extern __shared__ __attribute__((aligned(16))) double psm[];
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  double *Bs = psm;                                // (N+16) x 129, zero padded
-  double *sv = Bs + paths2_bs(N);                  // mean update, zero past N
-  double *aux = sv + paths2_vec(N);                // D^-1 B^T (mean update), zero past N
-  double *pn = aux + paths2_vec(N);                // p_sigma squares, zero past N
-  __shared__ int hs;
-  const double cs = sc->sigmaCumulationFactor, effMu = sc->effectiveMu, cc = sc->cumulativeCovariance;
-  // eight loads in flight per thread (one at a time, the L2 round trips were the kernel's time)
-  for (int q0 = tid; q0 < (N + 16) * PA2_LD; q0 += 8 * 256) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int q = q0 + u * 256, e = q / PA2_LD, d = q - e * PA2_LD;
-      v[u] = (q < (N + 16) * PA2_LD && e < N && d < N) ? B[(size_t)e * N + d] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      const int q = q0 + u * 256;
-      if (q < (N + 16) * PA2_LD) Bs[q] = v[u];
-    }
-  }
-  for (int q = tid; q < 3 * (int)paths2_vec(N); q += 256) sv[q] = (q < N) ? meanUpdate[q] : 0.0;
-  __syncthreads();
-  const unsigned nb = __builtin_amdgcn_readfirstlane((unsigned)(N + 7) >> 3);
-  const int d = lane + 64 * (wid & 1);  // waves 0-1: rows d < 128
-  // aux[d] = (sum_e B[e][d] mu[e]) / D[d]   (CMAES.cpp.base:627-636)
-  if (wid < 2) {
-    const double a1 = chains::kc_lock_asc<PA2_LD * 8>(0.0, lds_addr(sv), lds_addr(Bs + d), nb);
-    if (d < N) {
-      const double a = a1 / D[d];
-      aux[d] = a;
-      auxBDZ[d] = a;
-    }
-  }
-  __syncthreads();
-  // p_sigma = (1-c_s) p_sigma + sqrt(c_s (2-c_s) mu_eff) sum_e B[d][e] aux[e]   (:641-656)
-  const double fac = sqrt(cs * (2. - cs) * effMu);
-  if (wid < 2) {
-    const double sum = chains::kc_lock_asc<8>(0.0, lds_addr(aux), lds_addr(Bs + (size_t)d * PA2_LD), nb);
-    if (d < N) {
-      const double p = (1. - cs) * ps[d] + fac * sum;
-      ps[d] = p;
-      pn[d] = p * p;  // std::pow(x, 2.0) == x*x (CR)
-    }
-  }
-  __syncthreads();
-  if (wid == 0) {
-    const double nrm2 = chains::kc_add(0.0, lds_addr(pn), __builtin_amdgcn_readfirstlane((unsigned)(N + 15) >> 4));
-    if (lane == 0) {
-      const double nrm = sqrt(nrm2);
-      sc->psNorm = nrm;
-      const int hsig = (1.4 + 2.0 / (N + 1) > nrm / sqrt(1. - hsig_pow(sc, cs, gen)) /
-                                                   sc->chiSquareNumber);
-      hs = hsig;
-      sc->hsig = hsig;
-      const double a = N + 1.3, b = N + 2.0;
-      const double ccov1 = 2.0 / (a * a + effMu);
-      double ccovmu = 2.0 * (effMu - 2. + 1. / effMu) / (b * b + effMu);
-      if (1.0 - ccov1 < ccovmu) ccovmu = 1.0 - ccov1;
-      sc->ccov1 = ccov1;
-      sc->ccovmu = ccovmu;
-    }
-  }
-  __syncthreads();
-  const double fac2 = sqrt(cc * (2. - cc) * effMu);
-  for (int q = tid; q < N; q += 256) pc[q] = (1. - cc) * pc[q] + hs * fac2 * meanUpdate[q];
-}
-
 // evolution paths :626-662 (+ the adaptC constants :693-694).  Both
 // matrix-vector products keep the reference's sequential e-order per output;
 // B is staged through LDS in column chunks so row sweeps stay coalesced.
@@ -2608,60 +2131,12 @@ __global__ void __launch_bounds__(1024) k_paths(int N, int diagonal, unsigned lo
   for (int d = tid; d < N; d += blockDim.x) pc[d] = (1. - cc) * pc[d] + hs * fac2 * meanUpdate[d];
 }
 
-// adaptC :690-707, exact: one thread per lower-triangle element, the rank-μ
-// sum sequential over k exactly as the reference evaluates it.
-constexpr int AC_T = 16, AC_K = 64;
 __device__ inline void tri_tile(int t, int &td, int &te) {
   int r = (int)((sqrt(8.0 * t + 1.0) - 1.0) / 2.0);
   while ((r + 1) * (r + 2) / 2 <= t) r++;
   while (r * (r + 1) / 2 > t) r--;
   td = r;
   te = t - r * (r + 1) / 2;
-}
-
-__global__ void __launch_bounds__(256) k_adaptC_exact(int N, int mu, int diagonal, const double *__restrict__ X,
-                                                      const unsigned *__restrict__ idx, const double *__restrict__ w,
-                                                      const double *__restrict__ prevMean,
-                                                      const double *__restrict__ pc, double *C,
-                                                      const CmaesScalars *__restrict__ sc) {
-  __shared__ double Yd[AC_K][AC_T], Ye[AC_K][AC_T], cw[AC_K];
-  int td, te;
-  tri_tile(blockIdx.x, td, te);
-  const int tid = threadIdx.x, ty = tid / AC_T, tx = tid % AC_T;
-  const int d = td * AC_T + ty, e = te * AC_T + tx;
-  const bool active = (d < N && e < N && e <= d && (!diagonal || e == d));
-  const double ccov1 = sc->ccov1, ccovmu = sc->ccovmu, cc = sc->cumulativeCovariance;
-  const int hsig = (int)sc->hsig;
-  const double sigmasquare = sc->sigma * sc->sigma;
-  double c = 0.0;
-  if (active) {
-    const double Cde = C[(size_t)d * N + e];
-    c = (1 - ccov1 - ccovmu) * Cde + ccov1 * (pc[d] * pc[e] + (1 - hsig) * cc * (2. - cc) * Cde);
-  }
-  for (int k0 = 0; k0 < mu; k0 += AC_K) {
-    const int kn = (mu - k0) < AC_K ? (mu - k0) : AC_K;
-    for (int q = tid; q < AC_K * AC_T; q += 256) {
-      const int kk = q / AC_T, cidx = q % AC_T;
-      double yd = 0.0, ye = 0.0;
-      if (kk < kn) {
-        const size_t row = (size_t)(k0 + kk) * N;  // Y row k = X[idx[k]]
-        const int dd = td * AC_T + cidx, ee = te * AC_T + cidx;
-        if (dd < N) yd = X[row + dd] - prevMean[dd];
-        if (ee < N) ye = X[row + ee] - prevMean[ee];
-      }
-      Yd[kk][cidx] = yd;
-      Ye[kk][cidx] = ye;
-    }
-    for (int q = tid; q < kn; q += 256) cw[q] = ccovmu * w[k0 + q];
-    __syncthreads();
-    if (active)
-      for (int kk = 0; kk < kn; kk++) c += cw[kk] * Yd[kk][ty] * Ye[kk][tx] / sigmasquare;
-    __syncthreads();
-  }
-  if (active) {
-    C[(size_t)d * N + e] = c;
-    if (e < d) C[(size_t)e * N + d] = c;
-  }
 }
 
 // adaptC with the rank-μ sum on the FP64 matrix cores (the "MFMA"
@@ -3319,6 +2794,10 @@ struct kg_cmaes_s {
   // KORALI_AMD_FUSED_DRAW=0 (A/B, read likewise): the separate transform and
   // objective kernels
   bool fusedDraw = true;
+  // KORALI_AMD_ADAPTC_LANE_MIN (read likewise): the exact covariance update
+  // runs on lane chains (k_adaptC_lane) from this N up, on row chains
+  // (k_adaptC_row) below it
+  int laneMin = 256;
   unsigned *meanArrived = nullptr;  // k_mean3<true>'s arrival counter (zero from create's fill, then monotonic)
   unsigned meanTarget = 0;          // its value once the launch enqueued last has arrived
   MtStream normal, uniform;
@@ -3738,11 +3217,8 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
     const size_t pbytes = ((size_t)N * (PA_EC + 1) + N) * sizeof(double);
     if (pbytes > 64 * 1024)
       KG_HIP(allow_dynamic_lds((const void *)k_paths, (int)pbytes));
-    KG_HIP(allow_dynamic_lds((const void *)k_mean2, (int)mean2_lds_bytes()));
     if (N <= 128)
       KG_HIP(allow_dynamic_lds((const void *)k_objective2, (int)ob2_lds_bytes(N)));
-    if (N <= 128)
-      KG_HIP(allow_dynamic_lds((const void *)k_paths2, (int)paths2_lds_bytes(N)));
   }
   if (rc) {
     delete h;
@@ -3770,6 +3246,8 @@ int kg_cmaes_create(const kg_cmaes_cfg *cfg, kg_cmaes_t *out) {
     h->earlyPub = !(e && *e == '0');
     e = getenv("KORALI_AMD_FUSED_DRAW");
     h->fusedDraw = !(e && *e == '0');
+    e = getenv("KORALI_AMD_ADAPTC_LANE_MIN");
+    if (e && *e) h->laneMin = atoi(e);
   }
   if (set_current(h, h->lamCfg, h->muCfg)) return 1;
   KG_HIP(hipMemcpy(h->lb, lb.data(), N * sizeof(double), hipMemcpyHostToDevice));
@@ -4240,43 +3718,53 @@ static int cmaes_sigma(kg_cmaes_t h, size_t gen) {
 }
 
 
-// KORALI_AMD_ROWCHAINS=0: the round-3 lockstep-lane mean / paths kernels (A/B)
-// the exact rank-mu sums on lane chains (k_adaptC_lane) from N = 256 up:
-// measured round 5 (gpurun_out/r5z) C4 (N = 512) 3.75 -> 2.14 ms per
-// generation, C2 (N = 128: 36 tiles, a third of the chip) 0.036 -> 0.060 ms,
-// so C2 keeps the row chains (KORALI_AMD_ADAPTC_LANE_MIN moves the switch)
-static bool lane_chains(int N) {
-  static const int from = [] {
-    const char *e = getenv("KORALI_AMD_ADAPTC_LANE_MIN");
-    return e && *e ? atoi(e) : 256;
-  }();
-  return N >= from;
-}
-static bool row_chains() {
-  static const bool on = [] {
-    const char *e = getenv("KORALI_AMD_ROWCHAINS");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
-
-static void launch_mean3(kg_cmaes_t h) {
-  hipLaunchKernelGGL(k_mean3<false>, dim3((h->N + 15) / 16), dim3(256), 0, h->stream, h->N, h->mu, h->Y, h->w, h->mean,
-                     h->prevMean, h->meanUpdate, h->sc, 0ULL, (const double *)nullptr, (const double *)nullptr,
-                     (double *)nullptr, (double *)nullptr, (double *)nullptr, (unsigned *)nullptr, 0u);
+// adaptC's exact rank-mu sums over share `rank` of `ranks` of the covariance
+// tiles, into C or, with `pack`, into the packed lower triangle.  Row chains
+// (k_adaptC_row) below N = h->laneMin, lane chains (k_adaptC_lane) from there
+// up: measured round 5, C4 (N = 512) 3.75 -> 2.14 ms per generation on lane
+// chains, C2 (N = 128: 36 tiles, a third of the chip) 0.036 -> 0.060 ms.
+// Either kernel picks Markstein quotients or true division per launch from
+// k_rankmu_prep's range flag.  While profiling, prof["adaptC_row" /
+// "adaptC_lane"] counts the launches (a host count, no events).
+static void cmaes_adaptC_exact(kg_cmaes_t h, int rank, int ranks, double *pack) {
+  const int N = h->N;
+  const bool lane = N >= h->laneMin;
+  const int nt = lane ? al_tiles(N) : ar_tiles(N);
+  const int t0 = (int)((long long)nt * rank / ranks), t1 = (int)((long long)nt * (rank + 1) / ranks);
+  if (t1 <= t0) return;
+  if (lane)
+    hipLaunchKernelGGL(k_adaptC_lane, dim3(t1 - t0), dim3(256), 0, h->stream, N, h->mu, h->cfg.diagonal_covariance,
+                       h->Yc, h->Tt, h->pc, h->C, h->sc, t0, pack);
+  else
+    hipLaunchKernelGGL(k_adaptC_row, dim3(t1 - t0), dim3(AR_NT), 0, h->stream, N, h->mu, h->cfg.diagonal_covariance,
+                       h->Yc, h->Tt, h->pc, h->C, h->sc, t0, pack);
+  if (h->profile) h->prof[lane ? "adaptC_lane" : "adaptC_row"].second += 1;
 }
 
+// the exact factors Yc / T of the selected rows in Y (k_rankmu_prep)
+static void cmaes_rankmu_prep(kg_cmaes_t h) {
+  const int N = h->N, mu = h->mu;
+  hipLaunchKernelGGL(k_rankmu_prep, dim3((mu + RP_T - 1) / RP_T, (N + RP_T - 1) / RP_T), dim3(256), 0, h->stream, N,
+                     mu, h->Y, h->w, h->prevMean, h->sc, h->Yc, h->Tt);
+}
+
+// adaptC from rank-mu partial sums (the MFMA mode's K-slices, or a sharded
+// handle's reduced partials, which still lack the factor ccovmu): one
+// workgroup per 16 x 16 tile of the lower triangle
+static int cov_tiles(int N) { return (N + 15) / 16 * ((N + 15) / 16 + 1) / 2; }
+static void cmaes_adaptC_combine(kg_cmaes_t h, int kslices, const double *part, int scaleByCcovmu) {
+  const int ntiles = cov_tiles(h->N);
+  hipLaunchKernelGGL(k_adaptC_combine, dim3(ntiles), dim3(256), 0, h->stream, h->N, kslices, ntiles,
+                     h->cfg.diagonal_covariance, part, h->pc, h->C, h->sc, scaleByCcovmu);
+}
+
+// the evolution paths: k_paths3 for N <= 128 with a full covariance, k_paths
+// otherwise
 static int cmaes_paths(kg_cmaes_t h, size_t generation) {
   const int N = h->N;
-  if (N <= 128 && !h->cfg.diagonal_covariance && row_chains()) {
+  if (N <= 128 && !h->cfg.diagonal_covariance) {
     hipLaunchKernelGGL(k_paths3, dim3(1), dim3(PR_T), 0, h->stream, N, (unsigned long long)generation, h->B, h->D,
                        h->meanUpdate, h->auxBDZ, h->ps, h->pc, h->sc);
-    KG_HIP(hipGetLastError());
-    return 0;
-  }
-  if (N <= 128 && !h->cfg.diagonal_covariance) {
-    hipLaunchKernelGGL(k_paths2, dim3(1), dim3(256), paths2_lds_bytes(N), h->stream, N, (unsigned long long)generation,
-                       h->B, h->D, h->meanUpdate, h->auxBDZ, h->ps, h->pc, h->sc);
     KG_HIP(hipGetLastError());
     return 0;
   }
@@ -4286,6 +3774,21 @@ static int cmaes_paths(kg_cmaes_t h, size_t generation) {
                      h->auxBDZ, h->ps, h->pc, h->sc);
   KG_HIP(hipGetLastError());
   return 0;
+}
+
+// the mean of the selected rows in Y (k_mean3<false>; skipped when the caller
+// has formed the mean already), the gradient-informed step when the samples
+// carry gradients, then the evolution paths
+static int cmaes_mean_paths(kg_cmaes_t h, size_t generation, bool mean = true) {
+  const int N = h->N;
+  if (mean)
+    hipLaunchKernelGGL(k_mean3<false>, dim3((N + 15) / 16), dim3(256), 0, h->stream, N, h->mu, h->Y, h->w, h->mean,
+                       h->prevMean, h->meanUpdate, h->sc, 0ULL, (const double *)nullptr, (const double *)nullptr,
+                       (double *)nullptr, (double *)nullptr, (double *)nullptr, (unsigned *)nullptr, 0u);
+  if (h->G)  // (a sharded handle: every rank holds the whole population's gradients, the caller's all-gather)
+    hipLaunchKernelGGL(k_mean_gradient, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, h->mu,
+                       h->cfg.gradient_step_size, h->G, h->idx, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
+  return cmaes_paths(h, generation);
 }
 
 // ------------------------------------------------------------------ CCMA-ES
@@ -4510,8 +4013,7 @@ static bool fused_select(kg_cmaes_t h) {
 // lambda in k_rank_sort's range.  (h->updates changes only in k_sigma's
 // launch, so kg_cmaes_sample and the kg_cmaes_update after it agree.)
 static bool plain_update(kg_cmaes_t h) {
-  return h->shards == 1 && fused_select(h) && early_publish_on(h) && row_chains() && h->lam > 256 &&
-         h->lam <= RANK_MAX;
+  return h->shards == 1 && fused_select(h) && early_publish_on(h) && h->lam > 256 && h->lam <= RANK_MAX;
 }
 
 int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
@@ -4572,8 +4074,7 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
       KG_HIP(hipGetLastError());
       KG_HIP(hipEventRecord(h->evC, h->stream2));
     } else if (!fused) {
-      hipLaunchKernelGGL(k_rankmu_prep, dim3((mu + RP_T - 1) / RP_T, (N + RP_T - 1) / RP_T), dim3(256), 0,
-                         h->stream, N, mu, h->Y, h->w, h->prevMean, h->sc, h->Yc, h->Tt);
+      cmaes_rankmu_prep(h);
       KG_HIP(hipGetLastError());
     }
     if (plain && N <= 128 && !h->G) {
@@ -4586,41 +4087,17 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
                       &gen, &h->B, &h->D, &h->auxBDZ, &h->ps,   &h->pc,       &h->meanArrived, &target};
       KG_HIP(launch_resident((const void *)k_mean3<true>, dim3(nMean + 1), dim3(PR_T), args, 0, h->stream, true));
       h->meanTarget = target;  // (only a launch that was made adds to the counter)
-    } else {
-      if (row_chains())
-        launch_mean3(h);
-      else
-        hipLaunchKernelGGL(k_mean2, dim3((N + MN_D - 1) / MN_D), dim3(256), mean2_lds_bytes(), h->stream, N, mu,
-                           h->Y, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
-      if (h->G)
-        hipLaunchKernelGGL(k_mean_gradient, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, mu,
-                           h->cfg.gradient_step_size, h->G, h->idx, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
-      if (cmaes_paths(h, generation)) return 1;
+    } else if (cmaes_mean_paths(h, generation)) {
+      return 1;
     }
   }
   {
     Stage st(h, "covariance");
-    const int nt = (N + 15) / 16, ntiles = nt * (nt + 1) / 2;
     if (h->cfg.cov_mode == KG_COV_MFMA) {
       KG_HIP(hipStreamWaitEvent(h->stream, h->evC, 0));
-      hipLaunchKernelGGL(k_adaptC_combine, dim3(ntiles), dim3(256), 0, h->stream, N, h->kslices, ntiles,
-                         h->cfg.diagonal_covariance, h->covPart, h->pc, h->C, h->sc, 0);
+      cmaes_adaptC_combine(h, h->kslices, h->covPart, 0);
     } else {
-      static const bool old2 = getenv("KORALI_AMD_ADAPTC2") != nullptr;  // A/B switch
-      if (!old2 && lane_chains(N)) {
-        hipLaunchKernelGGL(k_adaptC_lane, dim3(al_tiles(N)), dim3(256), 0, h->stream, N, mu,
-                           h->cfg.diagonal_covariance, h->Yc, h->Tt, h->pc, h->C, h->sc, 0, (double *)nullptr);
-      } else if (!old2 && row_chains()) {
-        // Markstein quotients when every factor is in range (k_rankmu_prep's
-        // flag, read on the device: the kernel picks the branch per launch)
-        hipLaunchKernelGGL(k_adaptC_row, dim3(ar_tiles(N)), dim3(AR_NT), 0, h->stream, N, mu,
-                           h->cfg.diagonal_covariance, h->Yc, h->Tt, h->pc, h->C, h->sc, 0, (double *)nullptr);
-      } else if (old2)
-        hipLaunchKernelGGL(k_adaptC_exact2, dim3((N + 3) / 4, (N + 63) / 64), dim3(256), 0, h->stream, N, mu,
-                           h->cfg.diagonal_covariance, h->Yc, h->Tt, h->pc, h->C, h->sc);
-      else
-        hipLaunchKernelGGL(k_adaptC_exact3, dim3(ax3_slots(N)), dim3(64 * (AX3_P + 1)), 0, h->stream, N, mu,
-                           h->cfg.diagonal_covariance, h->Yc, h->Tt, h->pc, h->C, h->sc);
+      cmaes_adaptC_exact(h, 0, 1, nullptr);
     }
     KG_HIP(hipGetLastError());
   }
@@ -4633,29 +4110,24 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
 int kg_cmaes_update_partial(kg_cmaes_t h, size_t generation) {
   const int N = h->N, mu = h->mu;
   if (cmaes_sort(h)) return 1;
-  if (h->covPack) {
-    // exact order: best bookkeeping, then this rank's selected rows into its
-    // exchange block
-    Stage st(h, "mean_paths");
-    const int per = h->lam / h->shards;
-    hipLaunchKernelGGL(k_update_best, dim3(1), dim3(256), 0, h->stream, N, mu, h->cfg.mu_type,
-                       (unsigned long long)generation, (const double *)nullptr, h->F, h->idx, h->w, h->currBestVars,
-                       h->bestEverVars, h->sc, (const int *)nullptr, h->lam);
-    if (h->rows) {
-      hipLaunchKernelGGL(k_shard_positions, dim3(1), dim3(1024), 0, h->stream, mu, per, h->shards, h->idx, h->shardPos,
-                         h->shardCounts);
-      hipLaunchKernelGGL(k_shard_pack, dim3(mu), dim3(128), 0, h->stream, N, h->shardRank, per, h->shards, h->idx,
-                         h->shardPos, h->shardCounts, h->X, h->rows);
-    }
-    KG_HIP(hipGetLastError());
-    h->rowBlock = -1;
-    return 0;
-  }
   {
     Stage st(h, "mean_paths");
     hipLaunchKernelGGL(k_update_best, dim3(1), dim3(256), 0, h->stream, N, mu, h->cfg.mu_type,
                        (unsigned long long)generation, (const double *)nullptr, h->F, h->idx, h->w, h->currBestVars,
                        h->bestEverVars, h->sc, (const int *)nullptr, h->lam);
+    if (h->covPack) {
+      // exact order: this rank's selected rows into its exchange block
+      const int per = h->lam / h->shards;
+      if (h->rows) {
+        hipLaunchKernelGGL(k_shard_positions, dim3(1), dim3(1024), 0, h->stream, mu, per, h->shards, h->idx,
+                           h->shardPos, h->shardCounts);
+        hipLaunchKernelGGL(k_shard_pack, dim3(mu), dim3(128), 0, h->stream, N, h->shardRank, per, h->shards, h->idx,
+                           h->shardPos, h->shardCounts, h->X, h->rows);
+      }
+      KG_HIP(hipGetLastError());
+      h->rowBlock = -1;
+      return 0;
+    }
     hipLaunchKernelGGL(k_shard_select, dim3(1), dim3(1024), 0, h->stream, mu, h->r0, h->r1, h->idx, h->kidx,
                        h->shardCnt);
     hipLaunchKernelGGL(k_gather_owned, dim3(mu), dim3(128), 0, h->stream, N, h->X, h->idx, h->kidx, h->shardCnt, h->Y);
@@ -4665,7 +4137,7 @@ int kg_cmaes_update_partial(kg_cmaes_t h, size_t generation) {
   }
   {
     Stage st(h, "covariance");
-    const int nt = (N + 15) / 16, ntiles = nt * (nt + 1) / 2;
+    const int ntiles = cov_tiles(N);
     hipLaunchKernelGGL(k_rankmu_tile<true>, dim3(rankmu_grid(N, h->kslices)), dim3(256), 0, h->stream, N, 0,
                        h->shardCnt, h->kslices, h->Y, h->kidx, h->w, h->mean, h->sc, h->covPart);  // mean not yet advanced
     hipLaunchKernelGGL(k_part_reduce, dim3(ntiles), dim3(256), 0, h->stream, h->kslices, ntiles, h->covPart,
@@ -4701,18 +4173,9 @@ int kg_cmaes_update_rows(kg_cmaes_t h, size_t generation) {
     hipLaunchKernelGGL(k_shard_unpack, dim3(mu), dim3(128), 0, h->stream, N, per, h->shards, h->idx, h->shardPos,
                        h->shardCounts, (const double *)h->rows, h->X, h->Y, h->mean, h->prevMean, h->currBestVars,
                        h->bestEverVars, h->sc);
-    hipLaunchKernelGGL(k_rankmu_prep, dim3((mu + RP_T - 1) / RP_T, (N + RP_T - 1) / RP_T), dim3(256), 0, h->stream, N,
-                       mu, h->Y, h->w, h->prevMean, h->sc, h->Yc, h->Tt);
-    if (row_chains())
-      launch_mean3(h);
-    else
-      hipLaunchKernelGGL(k_mean2, dim3((N + MN_D - 1) / MN_D), dim3(256), mean2_lds_bytes(), h->stream, N, mu, h->Y,
-                         h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
-    if (h->G)  // every rank holds the whole population's gradients (the caller's all-gather)
-      hipLaunchKernelGGL(k_mean_gradient, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, mu, h->cfg.gradient_step_size,
-                         h->G, h->idx, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
+    cmaes_rankmu_prep(h);
     KG_HIP(hipGetLastError());
-    if (cmaes_paths(h, generation)) return 1;
+    if (cmaes_mean_paths(h, generation)) return 1;
   }
   {
     // this rank's contiguous share of the covariance tiles, each element's
@@ -4721,15 +4184,7 @@ int kg_cmaes_update_rows(kg_cmaes_t h, size_t generation) {
     const size_t npk = (size_t)N * (N + 1) / 2;
     hipLaunchKernelGGL(k_fill_min_i64, dim3((unsigned)std::min<size_t>((npk + 255) / 256, 1024)), dim3(256), 0,
                        h->stream, npk, (long long *)h->covPack);
-    const bool lane = lane_chains(N);
-    const int nt = lane ? al_tiles(N) : ar_tiles(N);
-    const int t0 = (int)((long long)nt * h->shardRank / h->shards), t1 = (int)((long long)nt * (h->shardRank + 1) / h->shards);
-    if (t1 > t0 && lane)
-      hipLaunchKernelGGL(k_adaptC_lane, dim3(t1 - t0), dim3(256), 0, h->stream, N, mu, h->cfg.diagonal_covariance,
-                         h->Yc, h->Tt, h->pc, h->C, h->sc, t0, h->covPack);
-    else if (t1 > t0)
-      hipLaunchKernelGGL(k_adaptC_row, dim3(t1 - t0), dim3(AR_NT), 0, h->stream, N, mu, h->cfg.diagonal_covariance, h->Yc,
-                         h->Tt, h->pc, h->C, h->sc, t0, h->covPack);
+    cmaes_adaptC_exact(h, h->shardRank, h->shards, h->covPack);
     KG_HIP(hipGetLastError());
   }
   h->rowBlock = -1;
@@ -4750,17 +4205,12 @@ int kg_cmaes_update_finalize(kg_cmaes_t h, size_t generation) {
     Stage st(h, "mean_paths");
     hipLaunchKernelGGL(k_shard_finalize, dim3((N + 255) / 256), dim3(256), 0, h->stream, N, h->part, h->mean,
                        h->prevMean, h->meanUpdate, h->currBestVars, h->bestEverVars, h->sc);
-    if (h->G)
-      hipLaunchKernelGGL(k_mean_gradient, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, h->mu,
-                         h->cfg.gradient_step_size, h->G, h->idx, h->w, h->mean, h->prevMean, h->meanUpdate, h->sc);
     KG_HIP(hipGetLastError());
-    if (cmaes_paths(h, generation)) return 1;
+    if (cmaes_mean_paths(h, generation, false)) return 1;  // (k_shard_finalize formed the mean)
   }
   {
     Stage st(h, "covariance");
-    const int nt = (N + 15) / 16, ntiles = nt * (nt + 1) / 2;
-    hipLaunchKernelGGL(k_adaptC_combine, dim3(ntiles), dim3(256), 0, h->stream, N, 1, ntiles,
-                       h->cfg.diagonal_covariance, h->part + 2 * (size_t)N, h->pc, h->C, h->sc, 1);
+    cmaes_adaptC_combine(h, 1, h->part + 2 * (size_t)N, 1);
     KG_HIP(hipGetLastError());
   }
   if (flush_consume(h)) return 1;

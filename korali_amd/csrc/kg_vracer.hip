@@ -377,6 +377,9 @@ __global__ void k_vr_bwd_out(int Bn, int H, int O, const float *__restrict__ G, 
 __device__ __forceinline__ void vr_adam_elem(long long j, float g, float *__restrict__ theta, float *__restrict__ m1,
                                              float *__restrict__ m2, const State *__restrict__ st, int l2,
                                              float l2imp) {
+  // fAdam::processResult (fAdam.cpp:64-91), optional L2 term
+  // (deepSupervisor.cpp.base:147-153); eta and the beta powers were advanced
+  // by the metadata kernel of the same update.
   const float b1 = 0.9f, b2 = 0.999f, eps = 1e-08f;
   const float f1 = 1.0f / (1.0f - st->b1p), f2 = 1.0f / (1.0f - st->b2p);
   if (l2) g -= l2imp * theta[j];
@@ -489,17 +492,6 @@ __global__ __launch_bounds__(256) void k_vr_multi(VrMulti J) {
     }
     b -= g.n;
   }
-}
-
-// fAdam::processResult (fAdam.cpp:64-91), optional L2 term
-// (deepSupervisor.cpp.base:147-153); eta and the beta powers were advanced
-// by the metadata kernel of the same update.
-__global__ void k_vr_adam(long long n, float *__restrict__ theta, const float *__restrict__ grad,
-                          float *__restrict__ m1, float *__restrict__ m2, const State *__restrict__ st, int l2,
-                          float l2imp) {
-  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  vr_adam_elem(j, grad[j], theta, m1, m2, st, l2, l2imp);
 }
 
 // ------------------------------------------------------------ replay memory

@@ -21,6 +21,15 @@ def free_port():
         return s.getsockname()[1]
 
 
+def shard_check(ranks, N, lam, gens, obj, backend, variant, cov, **env):
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
+           "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "tools", "shard_check.py"),
+           str(N), str(lam), str(gens), obj, backend, variant, cov]
+    env = dict(os.environ, OMP_NUM_THREADS="1", **env)
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "SHARD_CHECK PASS" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
 @pytest.mark.parametrize("ranks,N,lam,gens,obj,backend,variant,cov", [
     (2, 32, 256, 6, "rosenbrock", "gloo", "plain", "exact"),
     (4, 200, 1024, 4, "ackley", "gloo", "plain", "exact"),
@@ -39,12 +48,14 @@ def test_sharded_population_matches_unsharded(ranks, N, lam, gens, obj, backend,
     Variants bounded / mirrored / discrete / diagonal: every rank draws the
     whole population (the redraw walk, the +-z pairs and the discrete
     mutations are sequential over it) and evaluates and sums its own rows."""
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
-           "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "tools", "shard_check.py"),
-           str(N), str(lam), str(gens), obj, backend, variant, cov]
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "SHARD_CHECK PASS" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    shard_check(ranks, N, lam, gens, obj, backend, variant, cov)
+
+
+def test_sharded_lane_chains_pack_matches_unsharded():
+    """KORALI_AMD_ADAPTC_LANE_MIN=0: k_adaptC_lane writes each rank's share of
+    the packed lower triangle (N = 33: six 16 x 16 tiles, three per rank, the
+    last row block holding one row)."""
+    shard_check(2, 33, 256, 4, "rosenbrock", "gloo", "plain", "exact", KORALI_AMD_ADAPTC_LANE_MIN="0")
 
 
 @pytest.mark.parametrize("ranks,N,P,gens,mcl,burn,backend", [(2, 4, 600, 8, 1, 0, "gloo"), (3, 3, 500, 8, 3, 1, "gloo"),

@@ -8,6 +8,11 @@ mean + paths launch), so every run here has more than one generation; the
 shapes are the smallest at which these kernels can go wrong: N not a multiple
 of 4 or 16, odd lambda and odd mu, lambda just above the rank-sort threshold,
 a last workgroup with fewer than 16 keys, N at the k_paths3 limit.
+
+The exact covariance update runs on row chains (k_adaptC_row) below N = 256
+and on lane chains (k_adaptC_lane) from there up; KORALI_AMD_ADAPTC_LANE_MIN,
+read when the handle is created, moves the switch, and the profile counters
+adaptC_row / adaptC_lane tell which kernel ran.
 """
 import numpy as np
 import pytest
@@ -21,17 +26,19 @@ STATE = ("Current Mean", "Previous Mean", "Evolution Path", "Conjugate Evolution
          "Sigma", "Best Ever Value", "Best Ever Variables", "Current Best Value")
 
 
-def oracle_and_device(Nv, lam, seed=1337, mirrored=False):
+def oracle_and_device(Nv, lam, seed=1337, mirrored=False, diagonal=False):
     from korali_amd.native import CmaesDevice
     o = R.CMAES(Nv, lam, 0)
     o["Initial Value"] = np.zeros(Nv)
     o["Initial Standard Deviation"] = np.ones(Nv)
     if mirrored:
         o.option("Mirrored Sampling", 1)
+    if diagonal:
+        o.option("Diagonal Covariance", 1)
     R.lib().kr_rng_seed(o.rng(0).ptr, seed)
     R.lib().kr_rng_seed(o.rng(1).ptr, seed + 1)
     dev = CmaesDevice(Nv, lam, initial_value=np.zeros(Nv), initial_std=np.ones(Nv), normal_seed=seed,
-                      uniform_seed=seed + 1, cov_mode="exact", mirrored=mirrored)
+                      uniform_seed=seed + 1, cov_mode="exact", mirrored=mirrored, diagonal=diagonal)
     return o, dev
 
 
@@ -44,14 +51,21 @@ def assert_same_state(o, dev, g):
         assert np.array_equal(dev[key], o[key]), (g, key)
 
 
-def seeded_run(Nv, lam, gens, objective="rosenbrock", mirrored=False):
-    o, dev = oracle_and_device(Nv, lam, mirrored=mirrored)
+def seeded_run(Nv, lam, gens, objective="rosenbrock", mirrored=False, diagonal=False, adaptc=None):
+    """adaptc ("row" / "lane"): additionally, that kernel served every
+    generation's covariance update and the other one none."""
+    o, dev = oracle_and_device(Nv, lam, mirrored=mirrored, diagonal=diagonal)
+    if adaptc:
+        dev.profile()
     for g in range(1, gens + 1):
         o.generation(g, objective)
         dev.generation(g, objective)
         assert_same_state(o, dev, g)
     assert dev.get_rng(0) == o.rng(0).get_bytes()
     assert dev.get_rng(1) == o.rng(1).get_bytes()
+    if adaptc:
+        ran = {k: dev.profile_read("adaptC_" + k)[1] for k in ("row", "lane")}
+        assert ran == {"row": gens if adaptc == "row" else 0, "lane": gens if adaptc == "lane" else 0}, ran
     dev.close()
 
 
@@ -72,7 +86,37 @@ def test_old_path_still_matches(monkeypatch):
     both switches are read when the handle is created."""
     monkeypatch.setenv("KORALI_AMD_FUSED_SELECT", "0")
     monkeypatch.setenv("KORALI_AMD_EARLY_PUBLISH", "0")
-    seeded_run(17, 300, 4)
+    seeded_run(17, 300, 4, adaptc="row")
+
+
+# k_adaptC_lane below its default range (16 x 16 tiles, 64-term chunks summed
+# in groups of 8 with single terms after them; mu = lambda / 2)
+LANE_SHAPES = [
+    (5, 16, 6),     # mu = 8: one partial chunk, exactly one group of 8; the separate sort and selection kernels
+    (3, 257, 3),    # mu = 128: two full chunks (no load after the last one); one tile, mostly inactive lanes
+    (16, 272, 3),   # N fills one tile; mu = 136: two chunks and one group of 8, no singles
+    (17, 300, 4),   # three tiles, the second row block holds one row; mu = 150: 2 chunks, 2 groups of 8, 6 singles
+    (33, 1000, 3),  # six tiles; mu = 500: seven chunks and a tail of 52
+]
+
+
+@pytest.mark.parametrize("Nv,lam,gens", LANE_SHAPES)
+def test_lane_chains_match_oracle_bit_exact(monkeypatch, Nv, lam, gens):
+    monkeypatch.setenv("KORALI_AMD_ADAPTC_LANE_MIN", "0")
+    seeded_run(Nv, lam, gens, adaptc="lane")
+
+
+def test_lane_chains_with_separate_selection_kernels(monkeypatch):
+    """The factors come from k_rankmu_prep, not from the fused selection."""
+    monkeypatch.setenv("KORALI_AMD_ADAPTC_LANE_MIN", "0")
+    monkeypatch.setenv("KORALI_AMD_FUSED_SELECT", "0")
+    monkeypatch.setenv("KORALI_AMD_EARLY_PUBLISH", "0")
+    seeded_run(17, 300, 4, adaptc="lane")
+
+
+def test_lane_chains_diagonal_covariance(monkeypatch):
+    monkeypatch.setenv("KORALI_AMD_ADAPTC_LANE_MIN", "0")
+    seeded_run(17, 300, 3, diagonal=True, adaptc="lane")
 
 
 def test_select_prep_path_still_matches(monkeypatch):

@@ -535,7 +535,7 @@ int kg_tmcmc_set_gradients(kg_tmcmc_t h, const double *grad, const double *fishe
  *
  * logSumExp is auxiliar/math.hpp:205-225 operation for operation; log and exp
  * are the correctly rounded ones of the other likelihoods. */
-enum kg_hier_mode { KG_HIER_PSI = 0, KG_HIER_THETANEW = 1 };
+enum kg_hier_mode { KG_HIER_PSI = 0, KG_HIER_THETANEW = 1, KG_HIER_THETA = 2 /* kg_tmcmc_set_hierarchical_theta */ };
 
 typedef struct {
   int mode;                  /* enum kg_hier_mode */
@@ -566,6 +566,49 @@ int kg_tmcmc_set_hierarchical(kg_tmcmc_t h, const kg_tmcmc_hierarchical *d);
 /* The same kernel on `rows` arbitrary points X (rows x N, row-major), the
  * prior not consulted and NaN results returned as they are; waits. */
 int kg_tmcmc_hierarchical_loglik(kg_tmcmc_t h, const double *X, size_t rows, double *out);
+
+/* Hierarchical/Theta (phase 3b; theta.cpp.base:59-124): the
+ * posterior of one sub-experiment's parameters, informed by the Psi
+ * experiment's samples.  With S (sub_rows x D) / lpS the sub-experiment's
+ * "Sample Database" / "Sample LogPrior Database", Psi row i's conditional
+ * priors (a_i, b_i, cn_i) as KG_HIER_THETANEW forms them, K = sub_rows and
+ * M = psi_rows:
+ *
+ *   den_i = -log(K) + LSE_j( (0.0 + sum_k logdens_k(S[j][k]; i)) - lpS[j] )    once (:64-83)
+ *   LL(x) = (subLL(x) - log(M)) + LSE_i( (0.0 + sum_k logdens_k(x[k]; i)) - den_i )   (:97-124)
+ *
+ * subLL is the sub-problem's own log-likelihood: the handle's builtin kernel
+ * (kg_tmcmc_evaluate / _generation), or what kg_tmcmc_set_evaluations is
+ * given.  Everything is computed as written, infinities and NaN included. */
+typedef struct {
+  size_t prior_count;         /* D conditional priors (1..128) = the handle's variable_count */
+  const int *kind;            /* D, enum kg_prior_kind */
+  const int *param_index;     /* 2 D: Psi database column of each prior's first / second parameter, or -1 */
+  const double *param_const;  /* 2 D: the parameter where param_index is -1 */
+  size_t psi_rows, psi_width; /* the Psi experiment's "Sample Database" (M x psi_width, row-major) */
+  const double *psi_db;
+  size_t sub_rows;            /* the sub-experiment's "Sample Database" (K x D, row-major) ... */
+  const double *sub_db;
+  const double *sub_log_prior; /* ... and "Sample LogPrior Database" (K) */
+} kg_tmcmc_hier_theta;
+
+/* As kg_tmcmc_set_hierarchical (same place in a handle's life, same refusals,
+ * one hierarchical likelihood per handle); forms the denominators on the
+ * handle's stream and waits.  A Psi row with an invalid scale parameter is
+ * refused with the reference's message and the row.  From then on
+ * kg_tmcmc_evaluate_prior queues the LSE term of the pending chains beside
+ * the handle's stream (it depends on the candidates only, so it runs while
+ * the host evaluates the models), kg_tmcmc_set_evaluations completes the
+ * log-likelihoods it is given to LL(x), and kg_tmcmc_evaluate / _generation
+ * do both after the builtin kernel.  A NaN log-posterior is reported as
+ * kg_tmcmc_set_hierarchical describes, also by the two calls below. */
+int kg_tmcmc_set_hierarchical_theta(kg_tmcmc_t h, const kg_tmcmc_hier_theta *d);
+/* den (M = psi_rows doubles); waits. */
+int kg_tmcmc_theta_denominators(kg_tmcmc_t h, double *out, size_t M);
+/* LL of `rows` arbitrary points X (rows x D, row-major) with the sub-problem's
+ * log-likelihoods sub_loglik (rows; null: 0.0), the prior not consulted and
+ * NaN results returned as they are; waits. */
+int kg_tmcmc_theta_loglik(kg_tmcmc_t h, const double *X, size_t rows, const double *sub_loglik, double *out);
 int kg_tmcmc_profile(kg_tmcmc_t h, int enable);
 int kg_tmcmc_profile_read(kg_tmcmc_t h, const char *stage, double *ms_total, size_t *count);
 

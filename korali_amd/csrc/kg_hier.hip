@@ -1,9 +1,14 @@
-// kg_hier.hip — the Hierarchical/Psi and Hierarchical/ThetaNew log-likelihoods
-// (problem/hierarchical/psi/psi.cpp.base:120-141, thetaNew/thetaNew.cpp.base:
-// 35-54) on the device, for kg_tmcmc_* handles.
+// kg_hier.hip — the Hierarchical/Psi, Hierarchical/ThetaNew and Hierarchical/
+// Theta log-likelihoods (problem/hierarchical/psi/psi.cpp.base:120-141,
+// thetaNew/thetaNew.cpp.base:35-54, theta/theta.cpp.base:59-124) on the device,
+// for kg_tmcmc_* handles.
 //
-// Both are  LL(c) = sum_{g<G} [ LSE_{j<K_g}( base_{g,j} + sum_{k<D} logdens_k ) ]
-// (ThetaNew: G = 1 and -log(M) in front), with logSumExp as auxiliar/math.hpp:
+// All are  LL(c) = sum_{g<G} [ LSE_{j<K_g}( base_{g,j} + sum_{k<D} logdens_k ) ]
+// (ThetaNew: G = 1 and -log(M) in front; Theta: as ThetaNew with row j's
+// precomputed denominator subtracted from its term and the sub-problem's own
+// log-likelihood in front; Theta's denominators: one point per Psi row over
+// the sub-experiment's samples, their log-prior subtracted last and -log(K) in
+// front), with logSumExp as auxiliar/math.hpp:
 // 205-225 writes it: max by `>`, +-inf returned as it is, else the exponentials
 // of (v_j - max) added from 0.0 in j order, max + log(sum).
 //
@@ -35,6 +40,9 @@ constexpr int TPB = 256;    // lanes of a workgroup = rows of a tile
 // 1 = NaN log-posterior of a chain with a finite prior
 constexpr unsigned long long ST_CLEAR = ~0ull;
 
+// the fourth workgroup mode, internal: Theta's denominators (theta.cpp.base:64-83)
+constexpr int MODE_THETA_DEN = 3;
+
 struct Layout {
   int mode = 0, D = 0, G = 0, W = 0;  // W: doubles per point (Psi: handle's N; ThetaNew: D)
   size_t R = 0;                       // rows of all groups
@@ -53,7 +61,14 @@ struct Layout {
   unsigned long long *status = nullptr, *hStatus = nullptr;
   const double *lastX = nullptr;      // the points the last evaluation read (device)
   size_t lastLd = 0;
-  double negLogM = 0.0;               // ThetaNew: -log(M)
+  double negLogM = 0.0;               // ThetaNew, Theta: -log(M)
+  // Theta: row r's precomputed denominator (R), the sub-problem's
+  // log-likelihoods of kg_tmcmc_theta_loglik (xRows), and the stream the
+  // group kernel of a host-fed round runs on beside the handle's
+  double *den = nullptr, *sub = nullptr;
+  hipStream_t side = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  bool sidePending = false;
 };
 
 // the distributions' updateDistribution constants (uniform.cpp.base:38-44,
@@ -128,7 +143,10 @@ __global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t 
                                                    const unsigned long long *__restrict__ goff,
                                                    const double *__restrict__ A, const double *__restrict__ B,
                                                    const double *__restrict__ Cn, const double *__restrict__ base,
-                                                   double *__restrict__ part, unsigned long long *status) {
+                                                   const double *__restrict__ den, const double *__restrict__ pA,
+                                                   const double *__restrict__ pB, const double *__restrict__ pCn,
+                                                   size_t pR, double *__restrict__ part,
+                                                   unsigned long long *status) {
   __shared__ double sa[MAX_D], sb[MAX_D], sc[MAX_D];
   __shared__ int sk[MAX_D];
   __shared__ double tile[2][TPB];
@@ -142,7 +160,11 @@ __global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t 
   const double *x = X + c * ld;
   for (int k = t; k < D; k += TPB) {
     sk[k] = kind[k];
-    if (MODE == KG_HIER_PSI) {  // updateConditionalPriors (psi.cpp.base:110-118)
+    if (MODE == MODE_THETA_DEN) {  // Psi row c's conditional priors, as k_hier_setup left them
+      sa[k] = pA[(size_t)k * pR + c];
+      sb[k] = pB[(size_t)k * pR + c];
+      sc[k] = pCn[(size_t)k * pR + c];
+    } else if (MODE == KG_HIER_PSI) {  // updateConditionalPriors (psi.cpp.base:110-118)
       const double a = psrc[2 * k] >= 0 ? x[psrc[2 * k]] : pconst[2 * k];
       const double b = psrc[2 * k + 1] >= 0 ? x[psrc[2 * k + 1]] : pconst[2 * k + 1];
       sa[k] = a;
@@ -165,10 +187,15 @@ __global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t 
     if (MODE == KG_HIER_PSI) {
       v = base[r];  // psi.cpp.base:132
       for (int k = 0; k < D; k++) v += logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
+    } else if (MODE == MODE_THETA_DEN) {
+      v = 0.;  // theta.cpp.base:73-77: the sub-sample's log-prior (base, not negated) comes off last
+      for (int k = 0; k < D; k++) v += logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
+      v -= base[r];
     } else {
-      v = 0.;  // thetaNew.cpp.base:48
+      v = 0.;  // thetaNew.cpp.base:48, theta.cpp.base:116
       for (int k = 0; k < D; k++)
         v += logdens(sk[k], sa[k], sb[k], A[(size_t)k * R + r], B[(size_t)k * R + r], Cn[(size_t)k * R + r]);
+      if (MODE == KG_HIER_THETA) v -= den[r];  // theta.cpp.base:120
     }
     return v;
   };
@@ -206,10 +233,13 @@ __global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t 
 }
 
 // psi.cpp.base:124,137 (0.0, += each group) / thetaNew.cpp.base:53
-// (-log(M) + lse); hierarchical.cpp.base:51: a NaN log-posterior is an error
+// (-log(M) + lse; Theta's denominators theta.cpp.base:80 likewise with
+// -log(K)) / theta.cpp.base:123 ((subLL - log(M)) + lse; subll may be out
+// itself, or null for 0.0); hierarchical.cpp.base:51: a NaN log-posterior is
+// an error
 __global__ void k_hier_finish(int mode, int G, size_t npts, double negLogM, const unsigned char *__restrict__ pend,
-                              const double *__restrict__ lp, const double *__restrict__ part,
-                              double *__restrict__ out, unsigned long long *status) {
+                              const double *__restrict__ lp, const double *__restrict__ part, const double *subll,
+                              double *out, unsigned long long *status) {
   const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= npts) return;
   if (pend && !pend[c]) return;
@@ -218,6 +248,8 @@ __global__ void k_hier_finish(int mode, int G, size_t npts, double negLogM, cons
   if (mode == KG_HIER_PSI) {
     ll = 0.0;
     for (int g = 0; g < G; g++) ll += part[c * G + g];
+  } else if (mode == KG_HIER_THETA) {
+    ll = ((subll ? subll[c] : 0.0) + negLogM) + part[c];
   } else {
     ll = negLogM + part[c];
   }
@@ -230,11 +262,11 @@ __global__ void k_hier_neglog(double M, double *out) { out[0] = -log_cr(M); }
 
 inline unsigned nblocks(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
-// LL of npts points X (ld doubles apart) into out; pend / lp as the handle's
-// pending mask and log-priors, or null (every point, prior not consulted)
-inline int evaluate(Layout &L, const double *X, size_t ld, size_t npts, const unsigned char *pend, const double *lp,
-                    double *out, hipStream_t stream) {
-  if (npts == 0) return 0;
+// the group values of npts points X (ld doubles apart) into L.part; pend / lp
+// as the handle's pending mask and log-priors, or null (every point, prior not
+// consulted)
+inline int group(Layout &L, const double *X, size_t ld, size_t npts, const unsigned char *pend, const double *lp,
+                 hipStream_t stream) {
   KG_CHECK(npts * (size_t)L.G < 0x7fffffffull, "hierarchical likelihood: too many (point, group) pairs");
   if (L.partRows < npts) {
     if (L.part) dev_release(L.part, stream);
@@ -243,23 +275,66 @@ inline int evaluate(Layout &L, const double *X, size_t ld, size_t npts, const un
     L.partRows = npts;
   }
   const unsigned grid = (unsigned)(npts * (size_t)L.G);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TPB), 0, stream, L.D, L.G, L.W, L.R, npts, ld, X, pend, lp, L.kind,
+                       L.psrc, L.pconst, L.goff, L.A, L.B, L.Cn, L.base, L.den, (const double *)nullptr,
+                       (const double *)nullptr, (const double *)nullptr, (size_t)0, L.part, L.status);
+  };
   if (L.mode == KG_HIER_PSI)
-    hipLaunchKernelGGL(k_hier_group<KG_HIER_PSI>, dim3(grid), dim3(TPB), 0, stream, L.D, L.G, L.W, L.R, npts, ld, X,
-                       pend, lp, L.kind, L.psrc, L.pconst, L.goff, L.A, L.B, L.Cn, L.base, L.part, L.status);
+    launch(k_hier_group<KG_HIER_PSI>);
+  else if (L.mode == KG_HIER_THETA)
+    launch(k_hier_group<KG_HIER_THETA>);
   else
-    hipLaunchKernelGGL(k_hier_group<KG_HIER_THETANEW>, dim3(grid), dim3(TPB), 0, stream, L.D, L.G, L.W, L.R, npts, ld,
-                       X, pend, lp, L.kind, L.psrc, L.pconst, L.goff, L.A, L.B, L.Cn, L.base, L.part, L.status);
-  hipLaunchKernelGGL(k_hier_finish, dim3(nblocks(npts, 128)), dim3(128), 0, stream, L.mode, L.G, npts, L.negLogM, pend,
-                     lp, L.part, out, L.status);
+    launch(k_hier_group<KG_HIER_THETANEW>);
   KG_HIP(hipGetLastError());
   L.lastX = X;
   L.lastLd = ld;
   return 0;
 }
 
+// the points' LL from L.part into out (Theta: subll, the sub-problem's own
+// log-likelihoods, in front)
+inline int finish(Layout &L, size_t npts, const unsigned char *pend, const double *lp, const double *subll,
+                  double *out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_hier_finish, dim3(nblocks(npts, 128)), dim3(128), 0, stream, L.mode, L.G, npts, L.negLogM, pend,
+                     lp, L.part, subll, out, L.status);
+  KG_HIP(hipGetLastError());
+  return 0;
+}
+
+// LL of npts points X into out, both launches on one stream
+inline int evaluate(Layout &L, const double *X, size_t ld, size_t npts, const unsigned char *pend, const double *lp,
+                    const double *subll, double *out, hipStream_t stream) {
+  if (npts == 0) return 0;
+  if (group(L, X, ld, npts, pend, lp, stream)) return 1;
+  return finish(L, npts, pend, lp, subll, out, stream);
+}
+
+// Theta's denominators (theta.cpp.base:64-83) into L.den: one point per Psi
+// row, one group of K sub-samples whose columns S / logS (D x K) and
+// log-priors lpS (K) the caller holds; negLogK = -log_cr(K)
+inline int denominators(Layout &L, size_t K, const double *S, const double *logS, const double *lpS,
+                        const unsigned long long *goffK, double negLogK, double *part, hipStream_t stream) {
+  KG_CHECK(L.R < 0x7fffffffull, "hierarchical likelihood: too many (point, group) pairs");
+  hipLaunchKernelGGL(k_hier_group<MODE_THETA_DEN>, dim3((unsigned)L.R), dim3(TPB), 0, stream, L.D, 1, L.D, K, L.R,
+                     (size_t)0, (const double *)nullptr, (const unsigned char *)nullptr, (const double *)nullptr, L.kind,
+                     L.psrc, L.pconst, goffK, S, logS, (const double *)nullptr, lpS, (const double *)nullptr, L.A, L.B,
+                     L.Cn, L.R, part, L.status);
+  hipLaunchKernelGGL(k_hier_finish, dim3(nblocks(L.R, 128)), dim3(128), 0, stream, (int)MODE_THETA_DEN, 1, L.R, negLogK,
+                     (const unsigned char *)nullptr, (const double *)nullptr, part, (const double *)nullptr, L.den,
+                     L.status);
+  KG_HIP(hipGetLastError());
+  return 0;
+}
+
 inline void release(Layout &L) {
+  if (L.side) (void)hipStreamSynchronize(L.side);  // its last group kernel reads the arrays below
+  if (L.fork) (void)hipEventDestroy(L.fork);
+  if (L.join) (void)hipEventDestroy(L.join);
+  if (L.side) (void)hipStreamDestroy(L.side);
   for (void *p : {(void *)L.kind, (void *)L.psrc, (void *)L.pconst, (void *)L.goff, (void *)L.A, (void *)L.B,
-                  (void *)L.Cn, (void *)L.base, (void *)L.part, (void *)L.X, (void *)L.out, (void *)L.status})
+                  (void *)L.Cn, (void *)L.base, (void *)L.part, (void *)L.X, (void *)L.out, (void *)L.status,
+                  (void *)L.den, (void *)L.sub})
     if (p) dev_release(p);
   if (L.hStatus) host_release(L.hStatus);
   L = Layout();

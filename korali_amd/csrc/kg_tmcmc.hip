@@ -2130,6 +2130,17 @@ int tm_sync_dev(kg_tmcmc_s *h) {
   return 0;
 }
 
+// a Theta handle's group kernel of a host-fed round runs beside the handle's
+// stream (kg_tmcmc_evaluate_prior); whatever next touches the candidates, the
+// group values or the layout on the handle's stream goes behind it
+int tm_theta_join(kg_tmcmc_s *h) {
+  if (!h->hier || !h->hier->sidePending) return 0;
+  hier::Layout &L = *h->hier;
+  KG_HIP(hipStreamWaitEvent(h->stream, L.join, 0));
+  L.sidePending = false;
+  return 0;
+}
+
 // calculateSquaredCVDifference at the annealing search's points.  The
 // device returns cv2 for a whole batch of points from double-double sums; the
 // reference's own value differs from that by its rounding (std::accumulate,
@@ -3161,6 +3172,7 @@ static int tm_normal_priors(kg_tmcmc_t h) {
 int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
   const int N = h->N, P = h->P;
   const size_t PN = (size_t)P * N;
+  if (tm_theta_join(h)) return 1;
   if (h->zAhead) {
     // the normals formed ahead (during the last multinomial) are complete
     // before this generation's producer is queued behind them on the side
@@ -3246,15 +3258,43 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
 int kg_tmcmc_evaluate(kg_tmcmc_t h) {
   TmStage st(h, "evaluate");
   // a hierarchical handle: the log-priors (and -inf log-likelihoods below a
-  // -inf prior) here, the likelihood of the other pending chains after it
+  // -inf prior) here, the likelihood of the other pending chains after it;
+  // Theta: the sub-problem's builtin log-likelihood here, completed after it
+  const bool theta = h->hier && h->hier->mode == KG_HIER_THETA;
   hipLaunchKernelGGL(k_tm_evaluate, dim3(nblk(h->P, 128)), dim3(128), 0, h->stream, h->N, h->P,
-                     h->hier ? -1 : h->cfg.likelihood, h->cand, h->negLogWidth, h->pmin, h->pmax, h->vkind, h->candLL,
-                     h->candLP, h->pend);
+                     h->hier && !theta ? -1 : h->cfg.likelihood, h->cand, h->negLogWidth, h->pmin, h->pmax, h->vkind,
+                     h->candLL, h->candLP, h->pend);
   KG_HIP(hipGetLastError());
   if (h->hier) {
     TmStage sh(h, "hier_loglik");
-    return hier::evaluate(*h->hier, h->cand, (size_t)h->N, (size_t)h->P, h->pend, h->candLP, h->candLL, h->stream);
+    if (theta && tm_theta_join(h)) return 1;
+    return hier::evaluate(*h->hier, h->cand, (size_t)h->N, (size_t)h->P, h->pend, h->candLP, theta ? h->candLL : nullptr,
+                          h->candLL, h->stream);
   }
+  return 0;
+}
+
+// a Psi database row with an invalid scale parameter: the reference aborts at
+// the first evaluation (updateConditionalPriors, thetaNew.cpp.base:46; Theta
+// already in initialize, theta.cpp.base:69)
+static int tm_hier_check_rows(int D, const int *kind, const int *param_index, const double *param_const,
+                              const double *rows, size_t R, size_t W) {
+  for (size_t r = 0; r < R; r++)
+    for (int k = 0; k < D; k++) {
+      const int kd = kind[k], ix = param_index[2 * k + 1];
+      const double b = ix >= 0 ? rows[r * W + ix] : param_const[2 * k + 1];
+      if ((kd == KG_PRIOR_NORMAL || kd == KG_PRIOR_LOGNORMAL || kd == KG_PRIOR_LAPLACE || kd == KG_PRIOR_CAUCHY) &&
+          b <= 0.0) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (Psi sample %zu, conditional prior %d)",
+                 kd == KG_PRIOR_NORMAL      ? "Standard Deviation parameter of Normal"
+                 : kd == KG_PRIOR_LOGNORMAL ? "Sigma parameter of LogNormal"
+                 : kd == KG_PRIOR_LAPLACE   ? "Width parameter of Laplace"
+                                            : "Scale parameter of Cauchy",
+                 b, r, k);
+        KG_CHECK(false, msg);
+      }
+    }
   return 0;
 }
 
@@ -3296,26 +3336,7 @@ int kg_tmcmc_set_hierarchical(kg_tmcmc_t h, const kg_tmcmc_hierarchical *d) {
     goff[g + 1] = goff[g] + d->group_size[g];
   }
   const size_t R = goff.back(), W = d->row_width;
-  if (!psi) {
-    // a database row with an invalid scale parameter: the reference aborts at
-    // the first evaluation (updateConditionalPriors, thetaNew.cpp.base:46)
-    for (size_t r = 0; r < R; r++)
-      for (int k = 0; k < D; k++) {
-        const int kd = d->kind[k], ix = d->param_index[2 * k + 1];
-        const double b = ix >= 0 ? d->rows[r * W + ix] : d->param_const[2 * k + 1];
-        if ((kd == KG_PRIOR_NORMAL || kd == KG_PRIOR_LOGNORMAL || kd == KG_PRIOR_LAPLACE || kd == KG_PRIOR_CAUCHY) &&
-            b <= 0.0) {
-          char msg[200];
-          snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (Psi sample %zu, conditional prior %d)",
-                   kd == KG_PRIOR_NORMAL      ? "Standard Deviation parameter of Normal"
-                   : kd == KG_PRIOR_LOGNORMAL ? "Sigma parameter of LogNormal"
-                   : kd == KG_PRIOR_LAPLACE   ? "Width parameter of Laplace"
-                                              : "Scale parameter of Cauchy",
-                   b, r, k);
-          KG_CHECK(false, msg);
-        }
-      }
-  }
+  if (!psi && tm_hier_check_rows(D, d->kind, d->param_index, d->param_const, d->rows, R, W)) return 1;
   KG_HIP(hipSetDevice(h->cfg.device));
   auto *L = new hier::Layout();
   h->hier = L;  // released by kg_tmcmc_destroy, also after an error below
@@ -3358,6 +3379,7 @@ int kg_tmcmc_set_hierarchical(kg_tmcmc_t h, const kg_tmcmc_hierarchical *d) {
 
 int kg_tmcmc_hierarchical_loglik(kg_tmcmc_t h, const double *X, size_t rows, double *out) {
   KG_CHECK(h && h->hier, "kg_tmcmc_hierarchical_loglik: the handle has no hierarchical likelihood");
+  KG_CHECK(h->hier->mode != KG_HIER_THETA, "kg_tmcmc_hierarchical_loglik: a Theta handle takes kg_tmcmc_theta_loglik");
   KG_CHECK(rows == 0 || (X && out), "kg_tmcmc_hierarchical_loglik: null argument");
   if (rows == 0) return 0;
   hier::Layout &L = *h->hier;
@@ -3373,7 +3395,130 @@ int kg_tmcmc_hierarchical_loglik(kg_tmcmc_t h, const double *X, size_t rows, dou
     L.xRows = rows;
   }
   KG_HIP(hipMemcpyAsync(L.X, X, rows * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (hier::evaluate(L, L.X, N, rows, nullptr, nullptr, L.out, h->stream)) return 1;
+  if (hier::evaluate(L, L.X, N, rows, nullptr, nullptr, nullptr, L.out, h->stream)) return 1;
+  KG_HIP(hipMemcpyAsync(out, L.out, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return tm_sync_dev(h);
+}
+
+int kg_tmcmc_set_hierarchical_theta(kg_tmcmc_t h, const kg_tmcmc_hier_theta *d) {
+  KG_CHECK(h && d, "kg_tmcmc_set_hierarchical_theta: null argument");
+  KG_CHECK(!h->mt, "Hierarchical problems run with Version 'TMCMC' (mTMCMC needs gradients)");
+  KG_CHECK(!h->hier, "kg_tmcmc_set_hierarchical_theta: the handle already has a hierarchical likelihood");
+  KG_CHECK(!h->prepared, "kg_tmcmc_set_hierarchical_theta: call before the first kg_tmcmc_prepare");
+  KG_CHECK(d->prior_count >= 1 && d->prior_count <= (size_t)hier::MAX_D,
+           "kg_tmcmc_set_hierarchical_theta: 1..128 conditional priors");
+  KG_CHECK(d->psi_rows >= 1, "kg_tmcmc_set_hierarchical_theta: an empty Psi database");
+  KG_CHECK(d->sub_rows >= 1, "kg_tmcmc_set_hierarchical_theta: an empty sub-experiment database");
+  KG_CHECK(d->kind && d->param_index && d->param_const && d->psi_db && d->sub_db && d->sub_log_prior,
+           "kg_tmcmc_set_hierarchical_theta: null array");
+  const int D = (int)d->prior_count;
+  KG_CHECK(h->N == D, "Hierarchical/Theta: the handle must have as many variables as conditional priors");
+  KG_CHECK(d->psi_width >= 1 && d->psi_width <= 65536, "kg_tmcmc_set_hierarchical_theta: psi_width out of range");
+  KG_CHECK(d->psi_rows < 0x7fffffffull && d->sub_rows <= (size_t)1 << 40,
+           "kg_tmcmc_set_hierarchical_theta: database size out of range");
+  for (int k = 0; k < D; k++) {
+    KG_CHECK(d->kind[k] >= KG_PRIOR_UNIFORM && d->kind[k] <= KG_PRIOR_LOGNORMAL,
+             "kg_tmcmc_set_hierarchical_theta: kind entries must be KG_PRIOR_UNIFORM .. KG_PRIOR_LOGNORMAL");
+    for (int q = 0; q < 2; q++)
+      KG_CHECK(d->param_index[2 * k + q] >= -1 && d->param_index[2 * k + q] < (int)d->psi_width,
+               "kg_tmcmc_set_hierarchical_theta: param_index out of range");
+  }
+  const size_t M = d->psi_rows, W = d->psi_width, K = d->sub_rows;
+  if (tm_hier_check_rows(D, d->kind, d->param_index, d->param_const, d->psi_db, M, W)) return 1;
+  KG_HIP(hipSetDevice(h->cfg.device));
+  auto *L = new hier::Layout();
+  h->hier = L;  // released by kg_tmcmc_destroy, also after an error below
+  L->mode = KG_HIER_THETA;
+  L->D = D;
+  L->G = 1;
+  L->W = (int)W;
+  L->R = M;
+  const size_t DM = (size_t)D * M, DK = (size_t)D * K;
+  // what only the denominators read: the Psi and sub databases as given, the
+  // sub database's columns S and their logarithms, its log-priors, its one
+  // group's offsets and the M group values
+  double *psiDev = nullptr, *subDev = nullptr, *S = nullptr, *logS = nullptr, *lpS = nullptr, *part = nullptr;
+  unsigned long long *goffK = nullptr;
+  struct Scratch {
+    std::vector<void **> p;
+    ~Scratch() {
+      for (void **q : p)
+        if (*q) dev_release(*q);
+    }
+  } scratch{{(void **)&psiDev, (void **)&subDev, (void **)&S, (void **)&logS, (void **)&lpS, (void **)&part,
+             (void **)&goffK}};
+  if (tdalloc(&L->kind, D) | tdalloc(&L->psrc, 2 * D) | tdalloc(&L->pconst, 2 * D) | tdalloc(&L->goff, 2) |
+      tdalloc(&L->A, DM) | tdalloc(&L->B, DM) | tdalloc(&L->Cn, DM) | tdalloc(&L->base, 2) | tdalloc(&L->den, M) |
+      tdalloc(&L->status, 1) | tdalloc(&psiDev, M * W) | tdalloc(&subDev, DK) | tdalloc(&S, DK) | tdalloc(&logS, DK) |
+      tdalloc(&lpS, K) | tdalloc(&part, M) | tdalloc(&goffK, 2))
+    return 1;
+  KG_HIP(host_alloc(&L->hStatus, sizeof(unsigned long long), hipHostMallocDefault));
+  *L->hStatus = hier::ST_CLEAR;
+  KG_HIP(hipStreamCreateWithFlags(&L->side, hipStreamNonBlocking));
+  KG_HIP(hipEventCreateWithFlags(&L->fork, hipEventDisableTiming));
+  KG_HIP(hipEventCreateWithFlags(&L->join, hipEventDisableTiming));
+  const unsigned long long goffM[2] = {0, M}, goffKh[2] = {0, K};
+  KG_HIP(hipMemcpy(L->status, L->hStatus, sizeof(unsigned long long), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->kind, d->kind, D * sizeof(int), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->psrc, d->param_index, 2 * D * sizeof(int), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->pconst, d->param_const, 2 * D * sizeof(double), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(L->goff, goffM, sizeof goffM, hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(goffK, goffKh, sizeof goffKh, hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(psiDev, d->psi_db, M * W * sizeof(double), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(subDev, d->sub_db, DK * sizeof(double), hipMemcpyHostToDevice));
+  KG_HIP(hipMemcpy(lpS, d->sub_log_prior, K * sizeof(double), hipMemcpyHostToDevice));
+  // every Psi row's parameters and constants (ThetaNew's set-up), the sub
+  // database's columns (Psi's), -log(M) and -log(K) as theta.cpp.base:123, :80
+  hipLaunchKernelGGL(hier::k_hier_setup, dim3(nblk(DM, 256)), dim3(256), 0, h->stream, (int)KG_HIER_THETANEW, D, M,
+                     (int)W, L->kind, L->psrc, L->pconst, psiDev, L->A, L->B, L->Cn);
+  hipLaunchKernelGGL(hier::k_hier_setup, dim3(nblk(DK, 256)), dim3(256), 0, h->stream, (int)KG_HIER_PSI, D, K, D,
+                     L->kind, L->psrc, L->pconst, subDev, S, logS, (double *)nullptr);
+  hipLaunchKernelGGL(hier::k_hier_neglog, dim3(1), dim3(1), 0, h->stream, (double)M, L->base);
+  hipLaunchKernelGGL(hier::k_hier_neglog, dim3(1), dim3(1), 0, h->stream, (double)K, L->base + 1);
+  KG_HIP(hipGetLastError());
+  double negLog[2];
+  KG_HIP(hipMemcpyAsync(negLog, L->base, sizeof negLog, hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  L->negLogM = negLog[0];
+  {
+    TmStage st(h, "theta_denominators");
+    if (hier::denominators(*L, K, S, logS, lpS, goffK, negLog[1], part, h->stream)) return 1;
+  }
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int kg_tmcmc_theta_denominators(kg_tmcmc_t h, double *out, size_t M) {
+  KG_CHECK(h && h->hier && h->hier->mode == KG_HIER_THETA,
+           "kg_tmcmc_theta_denominators: the handle has no Hierarchical/Theta likelihood");
+  KG_CHECK(out && M == h->hier->R, "kg_tmcmc_theta_denominators: out must hold one double per Psi row");
+  KG_HIP(hipMemcpyAsync(out, h->hier->den, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return tm_sync_dev(h);
+}
+
+int kg_tmcmc_theta_loglik(kg_tmcmc_t h, const double *X, size_t rows, const double *sub_loglik, double *out) {
+  KG_CHECK(h && h->hier && h->hier->mode == KG_HIER_THETA,
+           "kg_tmcmc_theta_loglik: the handle has no Hierarchical/Theta likelihood");
+  KG_CHECK(rows == 0 || (X && out), "kg_tmcmc_theta_loglik: null argument");
+  if (rows == 0) return 0;
+  hier::Layout &L = *h->hier;
+  const size_t N = (size_t)h->N;
+  if (tm_theta_join(h)) return 1;
+  if (tm_sync_dev(h)) return 1;
+  if (L.xRows < rows) {
+    for (double **p : {&L.X, &L.out, &L.sub}) {
+      if (*p) dev_release(*p);
+      *p = nullptr;
+    }
+    L.xRows = 0;
+    KG_HIP(dev_alloc(&L.X, rows * N * sizeof(double)));
+    KG_HIP(dev_alloc(&L.out, rows * sizeof(double)));
+    KG_HIP(dev_alloc(&L.sub, rows * sizeof(double)));
+    L.xRows = rows;
+  }
+  KG_HIP(hipMemcpyAsync(L.X, X, rows * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (sub_loglik) KG_HIP(hipMemcpyAsync(L.sub, sub_loglik, rows * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (hier::evaluate(L, L.X, N, rows, nullptr, nullptr, sub_loglik ? L.sub : nullptr, L.out, h->stream)) return 1;
   KG_HIP(hipMemcpyAsync(out, L.out, rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return tm_sync_dev(h);
 }
@@ -3383,6 +3528,17 @@ int kg_tmcmc_evaluate_prior(kg_tmcmc_t h) {
   hipLaunchKernelGGL(k_tm_evaluate, dim3(nblk(h->P, 128)), dim3(128), 0, h->stream, h->N, h->P, -1, h->cand,
                      h->negLogWidth, h->pmin, h->pmax, h->vkind, h->candLL, h->candLP, h->pend);
   KG_HIP(hipGetLastError());
+  if (h->hier && h->hier->mode == KG_HIER_THETA) {
+    // the LSE term of the pending chains depends on the candidates and their
+    // log-priors only: on the side stream, while the host evaluates the models
+    hier::Layout &L = *h->hier;
+    if (tm_theta_join(h)) return 1;
+    KG_HIP(hipEventRecord(L.fork, h->stream));
+    KG_HIP(hipStreamWaitEvent(L.side, L.fork, 0));
+    if (hier::group(L, h->cand, (size_t)h->N, (size_t)h->P, h->pend, h->candLP, L.side)) return 1;
+    KG_HIP(hipEventRecord(L.join, L.side));
+    L.sidePending = true;
+  }
   KG_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -3409,6 +3565,13 @@ int kg_tmcmc_set_evaluations(kg_tmcmc_t h, const double *log_prior, const double
   hipLaunchKernelGGL(k_tm_set_pending, dim3(nblk(P, 256)), dim3(256), 0, h->stream, (int)P, h->pend, h->E, h->E + P,
                      h->candLP, h->candLL);
   KG_HIP(hipGetLastError());
+  if (h->hier && h->hier->mode == KG_HIER_THETA) {
+    // log_likelihood was the sub-problem's: theta.cpp.base:123 on the device
+    hier::Layout &L = *h->hier;
+    KG_CHECK(L.sidePending, "kg_tmcmc_set_evaluations: a Hierarchical/Theta handle needs kg_tmcmc_evaluate_prior first");
+    if (tm_theta_join(h)) return 1;
+    if (hier::finish(L, P, h->pend, h->candLP, h->candLL, h->candLL, h->stream)) return 1;
+  }
   KG_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -3511,6 +3674,7 @@ int kg_tmcmc_set_gradients(kg_tmcmc_t h, const double *grad, const double *fishe
 int kg_tmcmc_advance(kg_tmcmc_t h, size_t generation, size_t *pending) {
   const int N = h->N, P = h->P;
   KG_CHECK(h->step < h->maxSteps, "kg_tmcmc_advance: every chain has finished this generation");
+  if (tm_theta_join(h)) return 1;
   const int s = ++h->step;
   if (!h->rounds && h->mt && s < h->maxSteps) {
     // mTMCMC burn-in: the same candidates are evaluated again (tm_schedule)

@@ -569,9 +569,10 @@ const KeyList OPTIMIZATION_KEYS = {"Type", "Num Objectives", "Objective Function
                                    "Has Discrete Variables", "Objective Kernel"};
 const KeyList BAYESIAN_CUSTOM_KEYS = {"Type", "Likelihood Model", "Likelihood Kernel"};
 const KeyList BAYESIAN_REFERENCE_KEYS = {"Type", "Computational Model", "Reference Data", "Likelihood Model"};
-// hierarchical/psi/psi.config, hierarchical/thetaNew/thetaNew.config
+// hierarchical/psi/psi.config, hierarchical/thetaNew/thetaNew.config, hierarchical/theta/theta.config
 const KeyList HIERARCHICAL_PSI_KEYS = {"Type", "Sub Experiments", "Conditional Priors"};
 const KeyList HIERARCHICAL_THETANEW_KEYS = {"Type", "Psi Experiment"};
+const KeyList HIERARCHICAL_THETA_KEYS = {"Type", "Sub Experiment", "Psi Experiment"};
 
 void rejectProblemUnrecognised(Json &pb, const std::string &canonType);
 
@@ -602,14 +603,25 @@ void rejectProblemUnrecognised(Json &pb, const std::string &pt) {
   else if (pt == "bayesian/reference") rejectUnrecognised(pb, "Reference", {BAYESIAN_REFERENCE_KEYS}, {});
   else if (pt == "hierarchical/psi") rejectUnrecognised(pb, "Psi", {HIERARCHICAL_PSI_KEYS}, {});
   else if (pt == "hierarchical/thetanew") rejectUnrecognised(pb, "ThetaNew", {HIERARCHICAL_THETANEW_KEYS}, {});
+  else if (pt == "hierarchical/theta") {
+    // the generated parser's order: the mandatory settings, then what is left over
+    for (const char *key : {"Sub Experiment", "Psi Experiment"})
+      if (!pb.contains(key) || !pb[key].is_object())
+        fail(" + No value provided for mandatory setting: ['%s'] required by Theta (the other hierarchical problems "
+             "are 'Hierarchical/Psi' and 'Hierarchical/ThetaNew').\n", key);
+    rejectUnrecognised(pb, "Theta", {HIERARCHICAL_THETA_KEYS}, {});
+  }
 }
 
 // ---------------------------------------------------- hierarchical problems
 // Hierarchical/Psi and Hierarchical/ThetaNew (problem/hierarchical/psi/
 // psi.cpp.base, thetaNew/thetaNew.cpp.base): their log-likelihoods are sums
 // over the sample databases of finished experiments, evaluated on the device
-// (kg_tmcmc_set_hierarchical).  Everything below reads the configuration and
-// raises the reference's initialize() errors; no device call.
+// (kg_tmcmc_set_hierarchical).  Hierarchical/Theta (theta/theta.cpp.base) is
+// such a sum in front of the sub-problem's own log-likelihood
+// (kg_tmcmc_set_hierarchical_theta).  Everything below reads the
+// configuration and raises the reference's initialize() errors; no device
+// call.
 struct PriorKind {
   const char *type, *a, *b, *what;
   int kind;
@@ -628,6 +640,7 @@ struct HierarchicalSpec {
   std::vector<double> constants, rows, logPriors;
   std::vector<size_t> groupSizes;
   size_t width = 0;
+  std::vector<double> subRows, subLogPriors;  // Theta: the sub-experiment's databases
 };
 
 const Json *member(const Json &j, const char *key) {
@@ -782,6 +795,98 @@ void readThetaNew(const Json &js, size_t variableCount, HierarchicalSpec &hs) {
   if (variableCount != hs.kinds.size())
     fail("The Hierarchical Bayesian (Theta New) problem has %zu variables, the psi-problem %zu conditional priors; "
          "they must be as many.\n", variableCount, hs.kinds.size());
+}
+
+// Theta::initialize (theta.cpp.base:7-95).  The experiment's variables and
+// distributions become the sub-experiment's (:85-92) before anything reads
+// them.  The inherited distributions are the sub-experiment object's, which
+// its own initialize() seeded (:42-43, distribution.cpp.base:36-39): from the
+// sub-experiment's saved 'Random Seed' counter in its distribution order, or
+// with their saved seed and 'Range' if the sub-experiment preserved its
+// generator states; the Theta experiment's own counter serves its solver's
+// three generators only.  A resumed Theta run that preserves its own states
+// restores the Ranges its result file holds instead (the prior generators draw
+// in generation 1 only, so no sample depends on this).
+void readTheta(Json &js, bool resume, HierarchicalSpec &hs, std::vector<uint64_t> &distSeeds,
+               std::vector<std::vector<unsigned char>> &distStates) {
+  hs.mode = KG_HIER_THETA;
+  {
+    const Json &cjs = js;
+    const Json &pb = cjs.at("Problem");
+    const Json &psi = pb.at("Psi Experiment"), &sub = pb.at("Sub Experiment");
+    // the Psi experiment (:9-36)
+    const Json *ppb = member(psi, "Problem");
+    const Json *ptype = ppb ? member(*ppb, "Type") : nullptr;
+    if (!ptype || !ptype->is_string() || canon(ptype->getString()) != "hierarchical/psi")
+      fail("Psi experiment passed is not of type Hierarchical/Psi\n");
+    readConditionalPriors(psi, member(*ppb, "Conditional Priors"), hs);
+    const size_t D = hs.kinds.size();
+    const Json *pv = member(psi, "Variables");
+    hs.width = pv && pv->is_array() ? pv->size() : 0;
+    size_t M = 0;
+    if (hs.width == 0 || !readDatabases(psi, hs.width, hs.rows, hs.logPriors, M))
+      fail("Error reading the sample database from the psi-problem. Was it a sampling experiment?\n");
+    const Json *leaders = member(psi.at("Solver"), "Chain Leaders LogLikelihoods");
+    if (!leaders || !leaders->is_array() || leaders->size() != M)
+      fail("The psi-problem's 'Chain Leaders LogLikelihoods' (%zu) and 'Sample Database' (%zu) differ in length.\n",
+           leaders && leaders->is_array() ? leaders->size() : (size_t)0, M);
+    hs.groupSizes.push_back(M);
+    for (size_t j = 0; j < M; j++) {
+      const double expPrior = std::exp(hs.logPriors[j]);
+      if (!std::isfinite(expPrior))
+        fail("Non finite (%lf) prior has been detected at sample %zu in Psi problem.\n", expPrior, j);
+    }
+    // the sub-experiment (:38-57)
+    if (!finished(sub))
+      fail("The Hierarchical Bayesian (Theta) requires that the sub problem has run completely, but this one has "
+           "not.\n");
+    const Json *spb = member(sub, "Problem");
+    const Json *stype = spb ? member(*spb, "Type") : nullptr;
+    const std::string st = stype && stype->is_string() ? canon(stype->getString()) : std::string();
+    if (st != "bayesian/custom" && st != "bayesian/reference")
+      fail("The Hierarchical Bayesian (Theta) requires a 'Sub Experiment' whose problem is of type 'Bayesian/Custom' "
+           "or 'Bayesian/Reference' (is '%s').\n", stype && stype->is_string() ? stype->getString().c_str() : "");
+    const Json *sv = member(sub, "Variables");
+    const size_t nv = sv && sv->is_array() ? sv->size() : 0;
+    if (nv != D)
+      fail("The Hierarchical Bayesian (Theta) sub-problem has %zu variables, the psi-problem %zu conditional priors; "
+           "they must be as many.\n", nv, D);
+    size_t K = 0;
+    if (!readDatabases(sub, D, hs.subRows, hs.subLogPriors, K))
+      fail("Error reading the sample database from the sub-problem. Was it a sampling experiment?\n");
+    const Json *sl = member(sub.at("Solver"), "Chain Leaders LogLikelihoods");
+    if (!sl || !sl->is_array() || sl->size() != K)
+      fail("The sub-problem's 'Chain Leaders LogLikelihoods' (%zu) and 'Sample Database' (%zu) differ in length.\n",
+           sl && sl->is_array() ? sl->size() : (size_t)0, K);
+    for (size_t j = 0; j < K; j++) {
+      const double expPrior = std::exp(hs.subLogPriors[j]);
+      if (!std::isfinite(expPrior))
+        fail("Non finite (%lf) prior has been detected at sample %zu in sub problem.\n", expPrior, j);
+    }
+  }
+  // :85-92
+  Json &sub = js["Problem"]["Sub Experiment"];
+  const Json saved = js["Distributions"];
+  const bool own = resume && js["Preserve Random Number Generator States"].getBool();
+  const Json vars = sub["Variables"];
+  const Json dists = sub.contains("Distributions") ? sub["Distributions"] : Json::array();
+  js["Variables"] = vars;
+  js["Distributions"] = dists;
+  Seeder subSeeds{sub.contains("Random Seed") ? sub["Random Seed"].getUInt() : 0ULL,
+                  sub.contains("Preserve Random Number Generator States") &&
+                      sub["Preserve Random Number Generator States"].getBool()};
+  distSeeds.clear();
+  distStates.clear();
+  for (size_t d = 0; d < js["Distributions"].size(); d++) {
+    Json &dj = js["Distributions"][d];
+    distSeeds.push_back(subSeeds.assign(dj));
+    std::vector<unsigned char> stt(5000);
+    const Json *range = own && saved.is_array() && d < saved.size() ? member(saved.at(d), "Range") : nullptr;
+    if ((range && range->is_string() && parseHexState(range->getString(), stt.data())) || subSeeds.range(dj, stt.data()))
+      distStates.push_back(stt);
+    else
+      distStates.emplace_back();
+  }
 }
 
 // ------------------------------------------------------------- sharding
@@ -1450,8 +1555,9 @@ struct TmcmcModule : SolverModule {
     Json &sv = js["Solver"];
     Json &pb = js["Problem"];
     const std::string pt = canon(str(pb, "Type", ""));
-    const bool hierarchical = pt == "hierarchical/psi" || pt == "hierarchical/thetanew";
-    if (pt != "bayesian/custom" && pt != "bayesian/reference" && !hierarchical)
+    const bool hierarchical = pt == "hierarchical/psi" || pt == "hierarchical/thetanew";  // closed-form on the device
+    const bool theta = pt == "hierarchical/theta";
+    if (pt != "bayesian/custom" && pt != "bayesian/reference" && !hierarchical && !theta)
       fail("The device TMCMC path supports problems of type 'Bayesian/Custom' and 'Bayesian/Reference' (is '%s').",
            pb["Type"].getString().c_str());
     rejectUnrecognised(sv, "TMCMC", {SOLVER_KEYS, TMCMC_KEYS}, {SOLVER_TERMINATION, TMCMC_TERMINATION});
@@ -1465,9 +1571,18 @@ struct TmcmcModule : SolverModule {
     replicated = mtmcmc && dist;
     // TMCMC.cpp.base:48-55
     if (mtmcmc && !reference) fail("mTMCMC works only for problems of type 'Bayesian/Reference'\n");
+    HierarchicalSpec hs;
+    if (theta) {
+      if (dist)
+        fail("Problems of type 'Hierarchical/Theta' are out of scope for the Distributed conduit: run them with the "
+             "Sequential or the Concurrent conduit.");
+      readTheta(js, resume, hs, distSeeds, distStates);
+    }
+    // the problem whose likelihood the host or the builtin kernel evaluates: Theta's sub-problem
+    Json &lpb = theta ? pb["Sub Experiment"]["Problem"] : pb;
+    if (theta) reference = canon(str(lpb, "Type", "")) == "bayesian/reference";
     std::vector<VariableSpec> vars = readVariables(js);
     N = vars.size();
-    HierarchicalSpec hs;
     if (pt == "hierarchical/psi") readPsi(js, hs);
     if (pt == "hierarchical/thetanew") readThetaNew(js, N, hs);
     P = uint(sv, "Population Size", 0);
@@ -1528,22 +1643,22 @@ struct TmcmcModule : SolverModule {
     } else if (reference) {
       // Reference::initialize (reference.cpp.base:17-23) + the model checks
       // of evaluateLoglikelihood (:25-44)
-      if (!pb.contains("Computational Model") || !pb["Computational Model"].is_integer())
+      if (!lpb.contains("Computational Model") || !lpb["Computational Model"].is_integer())
         fail("Problem 'Bayesian/Reference' requires a 'Computational Model' function.");
-      fn = pb["Computational Model"].getUInt();
-      if (pb.contains("Reference Data") && pb["Reference Data"].is_array()) referenceData = flatten(pb["Reference Data"]);
-      likelihoodModel = str(pb, "Likelihood Model", "");
+      fn = lpb["Computational Model"].getUInt();
+      if (lpb.contains("Reference Data") && lpb["Reference Data"].is_array()) referenceData = flatten(lpb["Reference Data"]);
+      likelihoodModel = str(lpb, "Likelihood Model", "");
       if (referenceData.empty())
         fail("Bayesian (%s) problems require defining reference data.\n", likelihoodModel.c_str());
       if (!isReferenceLikelihoodModel(likelihoodModel))
         fail("Bayesian problem (%s) not recognized.\n", likelihoodModel.c_str());
-    } else if (pb.contains("Likelihood Kernel")) {
-      if (canon(pb["Likelihood Kernel"].getString()) != "gaussian")
-        fail("Unknown 'Likelihood Kernel' '%s'.", pb["Likelihood Kernel"].getString().c_str());
+    } else if (lpb.contains("Likelihood Kernel")) {
+      if (canon(lpb["Likelihood Kernel"].getString()) != "gaussian")
+        fail("Unknown 'Likelihood Kernel' '%s'.", lpb["Likelihood Kernel"].getString().c_str());
       builtin = true;
     } else {
-      if (!pb.contains("Likelihood Model")) fail("Problem 'Bayesian/Custom' requires a 'Likelihood Model'.");
-      fn = pb["Likelihood Model"].getUInt();
+      if (!lpb.contains("Likelihood Model")) fail("Problem 'Bayesian/Custom' requires a 'Likelihood Model'.");
+      fn = lpb["Likelihood Model"].getUInt();
     }
     // generators in TMCMC.config order: Multinomial, Multivariate, Uniform
     Json &gm = sv["Multinomial Generator"], &gv = sv["Multivariate Generator"], &gu = sv["Uniform Generator"];
@@ -1599,6 +1714,20 @@ struct TmcmcModule : SolverModule {
       d.rows = hs.rows.data();
       d.log_prior = hs.logPriors.data();
       check(kg_tmcmc_set_hierarchical(h, &d));
+    }
+    if (theta) {
+      kg_tmcmc_hier_theta d{};
+      d.prior_count = hs.kinds.size();
+      d.kind = hs.kinds.data();
+      d.param_index = hs.index.data();
+      d.param_const = hs.constants.data();
+      d.psi_rows = hs.groupSizes[0];
+      d.psi_width = hs.width;
+      d.psi_db = hs.rows.data();
+      d.sub_rows = hs.subLogPriors.size();
+      d.sub_db = hs.subRows.data();
+      d.sub_log_prior = hs.subLogPriors.data();
+      check(kg_tmcmc_set_hierarchical_theta(h, &d));
     }
     unsigned char st[5000];
     if (seeds.range(gm, st)) check(kg_tmcmc_set_rng(h, 0, st));
@@ -2682,15 +2811,15 @@ void runExperiment(Experiment &e, Conduit &conduit) {
   Collective *dist = conduit.dist.get();
   {
     // hierarchical problems: Psi and ThetaNew are closed-form sums on the
-    // device under TMCMC; Theta needs the sub-problem's computational model
+    // device under TMCMC; Theta is such a sum in front of the sub-problem's
+    // own log-likelihood
     const Json &cjs = js;
     const Json *pbt = cjs.contains("Problem") ? member(cjs.at("Problem"), "Type") : nullptr;
     const std::string ptype = pbt && pbt->is_string() ? canon(pbt->getString()) : std::string();
     if (ptype.rfind("hierarchical/", 0) == 0) {
-      if (ptype != "hierarchical/psi" && ptype != "hierarchical/thetanew")
-        fail("Problem type '%s' is not provided: of the hierarchical problems the device path supports "
-             "'Hierarchical/Psi' and 'Hierarchical/ThetaNew' ('Hierarchical/Theta' needs the sub-problem's "
-             "computational model).", pbt->getString().c_str());
+      if (ptype != "hierarchical/psi" && ptype != "hierarchical/thetanew" && ptype != "hierarchical/theta")
+        fail("Problem type '%s' is not provided: the hierarchical problems of the device path are "
+             "'Hierarchical/Psi', 'Hierarchical/ThetaNew' and 'Hierarchical/Theta'.", pbt->getString().c_str());
       if (stype != "sampler/tmcmc" && stype != "tmcmc")
         fail("Problems of type '%s' are supported with the 'Sampler/TMCMC' solver (is '%s').",
              pbt->getString().c_str(), sv["Type"].getString().c_str());

@@ -76,6 +76,15 @@ class _TmcmcHierarchical(C.Structure):
     ]
 
 
+class _TmcmcHierTheta(C.Structure):
+    _fields_ = [
+        ("prior_count", C.c_size_t), ("kind", C.POINTER(C.c_int)), ("param_index", C.POINTER(C.c_int)),
+        ("param_const", C.POINTER(C.c_double)), ("psi_rows", C.c_size_t), ("psi_width", C.c_size_t),
+        ("psi_db", C.POINTER(C.c_double)), ("sub_rows", C.c_size_t), ("sub_db", C.POINTER(C.c_double)),
+        ("sub_log_prior", C.POINTER(C.c_double)),
+    ]
+
+
 HIER_MODES = {"psi": 0, "thetanew": 1}
 PRIOR_KINDS = {"uniform": 0, "normal": 1, "exponential": 2, "laplace": 3, "cauchy": 4, "lognormal": 5}
 
@@ -115,6 +124,7 @@ EXPORTED = [
     "kg_tmcmc_evaluate", "kg_tmcmc_process", "kg_tmcmc_advance", "kg_tmcmc_get_pending",
     "kg_tmcmc_process_partial", "kg_tmcmc_process_finalize", "kg_tmcmc_device_ptr", "kg_tmcmc_stream", "kg_tmcmc_evaluate_prior", "kg_tmcmc_get_candidates", "kg_tmcmc_set_evaluations",
     "kg_tmcmc_set_gradients", "kg_tmcmc_set_hierarchical", "kg_tmcmc_hierarchical_loglik",
+    "kg_tmcmc_set_hierarchical_theta", "kg_tmcmc_theta_denominators", "kg_tmcmc_theta_loglik",
     "kg_tmcmc_profile", "kg_tmcmc_profile_read", "kg_debug_mt_jump", "kg_debug_multinomial", "kg_debug_cartpole",
     "kg_debug_cartpole_at",
     "kg_debug_host_tridiag", "kg_debug_host_chase",
@@ -212,6 +222,9 @@ def lib():
         L.kg_tmcmc_set_gradients.argtypes = [vp, dp, dp]
         L.kg_tmcmc_set_hierarchical.argtypes = [vp, C.POINTER(_TmcmcHierarchical)]
         L.kg_tmcmc_hierarchical_loglik.argtypes = [vp, dp, sz, dp]
+        L.kg_tmcmc_set_hierarchical_theta.argtypes = [vp, C.POINTER(_TmcmcHierTheta)]
+        L.kg_tmcmc_theta_denominators.argtypes = [vp, dp, sz]
+        L.kg_tmcmc_theta_loglik.argtypes = [vp, dp, sz, dp, dp]
         L.kg_tmcmc_advance.argtypes = [vp, sz, C.POINTER(sz)]
         L.kg_tmcmc_get_pending.argtypes = [vp, C.POINTER(C.c_ubyte)]
         L.kg_tmcmc_profile.argtypes = [vp, ip]
@@ -748,6 +761,58 @@ class TmcmcDevice:
         X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, self.N)
         out = np.empty(X.shape[0])
         check(self._L.kg_tmcmc_hierarchical_loglik(self.h, _dptr(X), X.shape[0], _dptr(out)))
+        return out
+
+    def set_hierarchical_theta(self, kinds, param_index, param_const, psi_db, sub_db, sub_log_priors):
+        """The Hierarchical/Theta likelihood (kg_tmcmc_set_hierarchical_theta),
+        before the first prepare: the handle's own log-likelihood (the builtin
+        kernel, or what set_evaluations is given) becomes the sub-problem's
+        and the device completes it.  kinds / param_index / param_const: the
+        Psi experiment's D conditional priors, as set_hierarchical("thetanew")
+        takes them; psi_db: its sample database (M x width); sub_db: the
+        sub-experiment's (K x D); sub_log_priors: its K log-priors."""
+        d = _TmcmcHierTheta()
+        kd = np.ascontiguousarray([PRIOR_KINDS[k.lower()] if isinstance(k, str) else int(k) for k in kinds],
+                                  dtype=np.int32)
+        D = kd.size
+        ix = np.ascontiguousarray(param_index, dtype=np.int32).reshape(-1)
+        cs = np.ascontiguousarray(param_const, dtype=np.float64).reshape(-1)
+        if ix.size != 2 * D or cs.size != 2 * D:
+            raise ValueError("set_hierarchical_theta: param_index / param_const must be D x 2")
+        psi = np.ascontiguousarray(psi_db, dtype=np.float64)
+        sub = np.ascontiguousarray(sub_db, dtype=np.float64)
+        lp = np.ascontiguousarray(sub_log_priors, dtype=np.float64).reshape(-1)
+        if psi.ndim != 2 or sub.ndim != 2 or sub.shape[1] != D:
+            raise ValueError("set_hierarchical_theta: psi_db must be M x width and sub_db K x D")
+        if lp.size != sub.shape[0]:
+            raise ValueError("set_hierarchical_theta: one log-prior per sub-experiment sample")
+        d.prior_count, d.kind = D, kd.ctypes.data_as(C.POINTER(C.c_int))
+        d.param_index, d.param_const = ix.ctypes.data_as(C.POINTER(C.c_int)), _dptr(cs)
+        d.psi_rows, d.psi_width, d.psi_db = psi.shape[0], psi.shape[1], _dptr(psi)
+        d.sub_rows, d.sub_db, d.sub_log_prior = sub.shape[0], _dptr(sub), _dptr(lp)
+        check(self._L.kg_tmcmc_set_hierarchical_theta(self.h, C.byref(d)))
+        self._theta_rows = psi.shape[0]
+
+    def theta_denominators(self):
+        """Theta's precomputed log-denominators, one per Psi sample
+        (kg_tmcmc_theta_denominators)."""
+        out = np.empty(getattr(self, "_theta_rows", 0))
+        check(self._L.kg_tmcmc_theta_denominators(self.h, _dptr(out), out.size))
+        return out
+
+    def theta_loglik(self, X, sub_loglik=None):
+        """The Hierarchical/Theta log-likelihood of arbitrary points (rows x N)
+        whose sub-problem log-likelihoods are sub_loglik (None: 0.0), the prior
+        not consulted (kg_tmcmc_theta_loglik)."""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, self.N)
+        out = np.empty(X.shape[0])
+        sub = None
+        if sub_loglik is not None:
+            sub = np.ascontiguousarray(sub_loglik, dtype=np.float64).reshape(-1)
+            if sub.size != X.shape[0]:
+                raise ValueError("theta_loglik: one sub-problem log-likelihood per point")
+        check(self._L.kg_tmcmc_theta_loglik(self.h, _dptr(X), X.shape[0], _dptr(sub) if sub is not None else None,
+                                            _dptr(out)))
         return out
 
     def field_size(self, name):

@@ -8,6 +8,17 @@ synthetic databases.
   ms of the likelihood kernels    stage "hier_loglik" (k_hier_group + k_hier_finish),
   ms per generation               host clock around kg_tmcmc_generation + synchronize.
 
+And of the Hierarchical/Theta likelihood at the example's phase 3b shape: P =
+1000 candidates, the phase-2 result's M = 2000 Psi samples, the phase-1
+result's K = 1000 sub-experiment samples, the same two conditional priors:
+
+  ms of the denominator set-up    stage "theta_denominators" of
+                                  kg_tmcmc_set_hierarchical_theta (k_hier_group's
+                                  denominator mode + k_hier_finish), one fresh
+                                  handle per sample,
+  ms of one evaluation round      stage "hier_loglik" of kg_tmcmc_evaluate
+                                  (k_hier_group's Theta mode + k_hier_finish).
+
 Warm-up first, then the median of at least 20 samples each.  tools/hier_cpu_loop
 (tools/hier_cpu_loop.cpp) times the same sums on one CPU core with libm.
 
@@ -40,6 +51,57 @@ def handle(seed):
                       multivariate_seed=seed + 5, uniform_seed=seed + 6)
     dev.set_hierarchical("psi", ["normal", "lognormal"], [[0, 1], [2, 3]], [[0.0, 0.0], [0.0, 0.0]], groups, lps)
     return dev
+
+
+TP, TM, TK = 1000, 2000, 1000
+
+
+def theta_handle(seed, profile):
+    from korali_amd.native import TmcmcDevice
+    rng = np.random.default_rng(2)
+    psi = np.stack([rng.uniform(-2.0, 2.0, TM), rng.uniform(0.2, 3.0, TM), rng.uniform(-1.0, 1.0, TM),
+                    rng.uniform(0.2, 2.0, TM)], axis=1)
+    sub = np.stack([1.5 * rng.standard_normal(TK), np.exp(0.2 + 0.6 * rng.standard_normal(TK))], axis=1)
+    dev = TmcmcDevice(2, TP, prior_min=[-4.0, 0.1], prior_max=[4.0, 5.0], prior_seeds=[seed, seed + 1],
+                      multinomial_seed=seed + 4, multivariate_seed=seed + 5, uniform_seed=seed + 6)
+    dev.profile(profile)
+    dev.set_hierarchical_theta(["normal", "lognormal"], [[0, 1], [2, 3]], [[0.0, 0.0], [0.0, 0.0]], psi, sub,
+                               rng.uniform(-6.0, -1.0, TK))
+    return dev
+
+
+def theta(samples):
+    theta_handle(5, False).close()  # warm-up: the code object, the allocator's blocks
+    den = []
+    for i in range(samples):
+        d = theta_handle(200 + 10 * i, True)
+        ms, n = d.profile_read("theta_denominators")
+        assert n == 1
+        den.append(ms)
+        if i + 1 < samples:
+            d.close()
+    d.profile(False)
+    d.prepare(1)
+    for _ in range(5):
+        d.evaluate()
+    d.synchronize()
+    d.profile(True)
+    hk = []
+    for _ in range(samples):
+        d.evaluate()
+        d.synchronize()
+        ms, n = d.profile_read("hier_loglik")
+        assert n == 1
+        hk.append(ms)
+    d.close()
+    out = {"theta_P": TP, "theta_psi_rows": TM, "theta_sub_rows": TK,
+           "theta_denominators_ms_median": statistics.median(den), "theta_denominators_ms_min": min(den),
+           "theta_denominators_ms_max": max(den), "theta_round_ms_median": statistics.median(hk),
+           "theta_round_ms_min": min(hk), "theta_round_ms_max": max(hk)}
+    exe = os.path.join(ROOT, "tools", "hier_cpu_loop")
+    if os.path.exists(exe):
+        out.update(json.loads(subprocess.check_output([exe, "theta", str(TP), str(TM), str(TK), "5"])))
+    return out
 
 
 def main():
@@ -87,6 +149,7 @@ def main():
     exe = os.path.join(ROOT, "tools", "hier_cpu_loop")
     if os.path.exists(exe):
         out.update(json.loads(subprocess.check_output([exe, str(P), str(G), str(K), "5"])))
+    out.update(theta(a.samples))
     line = json.dumps(out)
     print(line)
     if a.json:

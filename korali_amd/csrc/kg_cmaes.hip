@@ -4260,11 +4260,9 @@ int kg_cmaes_synchronize(kg_cmaes_t h) {
             "%d steps, %d rotations\n[korali_amd apply trace] groups %llu time-units %llu steps %llu ticks %llu\n"
             "[korali_amd multi-workgroup tridiag, writer wg] dnrm2 %llu householder %llu dsymv-stage %llu dsymv-chain "
             "%llu x-gather %llu xv-stage %llu xv-chain %llu alpha %llu pivot-poll %llu update %llu\n"
-            "[korali_amd streamed apply] batches %llu steps-before-chase-done %llu ticks-to-first-batch %llu\n"
-            "[korali_amd one-workgroup tridiag] householder %llu barrier %llu dsymv %llu xv %llu x-update %llu "
-            "pivot-update %llu chain-w0 %llu chain-w3 %llu (A: dnrm2 %llu [of which pre-chain %llu] scalars %llu)\n",
+            "[korali_amd streamed apply] batches %llu steps-before-chase-done %llu ticks-to-first-batch %llu\n",
             t[0], t[1], t[2], t[3], steps, rots, t[4], t[5], t[6], t[7], t[16], t[17], t[18], t[19], t[20], t[21],
-            t[22], t[23], t[24], t[25], t[26], t[27], t[28], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15], t[29], t[31], t[30]);
+            t[22], t[23], t[24], t[25], t[26], t[27], t[28]);
     fprintf(stderr,
             "[korali_amd sq tridiag, wave 0] staging %llu nrm2-chain %llu scalars+v %llu wait-A %llu dsymv %llu "
             "wait-E %llu xv+pivot %llu wait-X %llu\n",
@@ -4275,7 +4273,7 @@ int kg_cmaes_synchronize(kg_cmaes_t h) {
             t[16], t[17], t[18], t[19], t[20], t[21], t[22], t[23], t[24], t[25]);
     // the one-workgroup kernel's last launch, step by step: every phase's
     // ticks fitted as a + b n over the steps (n = N-1-i, the chain length)
-    if (h->eig.tridiag_kind() == 4) {
+    if (h->eig.tridiag_kind() == EigenPlan::Tridiag::Sq) {
       const int steps = h->N - 2;
       std::vector<unsigned long long> ps(8 * (size_t)steps);
       KG_HIP(hipMemcpy(ps.data(), h->eigTrace + 32, ps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));

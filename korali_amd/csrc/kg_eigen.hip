@@ -450,67 +450,6 @@ __device__ double dnrm2_wave(const double *x, int stride, int m, double *sv, uns
   return (m == 1) ? fabs(x[0]) : carry * sqrt(ssq);
 }
 
-// dnrm2_wave for m <= 128 (the one-workgroup tridiagonalisation): both
-// 64-element chunks are staged at once (independent DPP prefix maxima, one
-// division per element — before / a for a new maximum, a / before otherwise —
-// as a select of operands, no divergent branches), the rescale masks stay in
-// scalar registers; the ordered ssq recurrence is dnrm2_wave's.
-__device__ double dnrm2_wave128(const double *x, int m, double *sv) {
-  const int lane = threadIdx.x & 63;
-  const int m8 = (m + 7) & ~7;
-  const int e0 = lane, e1 = lane + 64;
-  const double r0 = fabs(x[min(e0, m - 1)]), r1 = fabs(x[min(e1, m - 1)]);
-  const double a0 = e0 < m ? r0 : 0.0, a1 = e1 < m ? r1 : 0.0;
-  const double pm0 = wave_prefix_max_nonneg(a0), pm1 = wave_prefix_max_nonneg(a1);
-  const double c0 = readlane_d(pm0, 63);
-  const double b0 = dpp_d<0x138, 0xf>(pm0);            // before, chunk 0 (lane 0: 0.0)
-  const double b1 = fmax(dpp_d<0x138, 0xf>(pm1), c0);  // before, chunk 1
-  const bool z0 = e0 < m && a0 != 0.0, z1 = e1 < m && a1 != 0.0;
-  const bool n0 = z0 && b0 < a0, n1 = z1 && b1 < a1;
-  const double q0 = (n0 ? b0 : a0) / (n0 ? a0 : b0), q1 = (n1 ? b1 : a1) / (n1 ? a1 : b1);
-  const unsigned long long k0 = __ballot(n0), k1 = __ballot(n1);
-  if (e0 < m8) sv[e0] = n0 ? q0 : (z0 ? q0 * q0 : 0.0);
-  if (e1 < m8) sv[e1] = n1 ? q1 : (z1 ? q1 * q1 : 0.0);
-  const double carry = fmax(c0, readlane_d(pm1, 63));
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  double ssq = 1.0;
-#define KG_NRM2_STEP8(T, BITS)                        \
-  {                                                   \
-    const unsigned bits_ = (BITS);                    \
-    if (bits_ == 0) {                                 \
-      _Pragma("unroll") for (int u = 0; u < 8; u++) ssq += T[u]; \
-    } else {                                          \
-      _Pragma("unroll") for (int u = 0; u < 8; u++) { \
-        if ((bits_ >> u) & 1u)                        \
-          ssq = 1.0 + ssq * T[u] * T[u];              \
-        else                                          \
-          ssq += T[u];                                \
-      }                                               \
-    }                                                 \
-  }
-  for (int cb = 0; cb < m8; cb += 64) {
-    const unsigned long long mw = cb ? k1 : k0;
-    const int cn = (m8 - cb) < 64 ? (m8 - cb) : 64;
-    double a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) a[u] = sv[cb + u];
-    for (int e = 0; e < cn; e += 16) {
-#pragma unroll
-      for (int u = 0; u < 8; u++) b[u] = sv[cb + e + 8 + u];
-      KG_NRM2_STEP8(a, (unsigned)((mw >> e) & 0xffULL))
-      if (e + 8 >= cn) break;
-#pragma unroll
-      for (int u = 0; u < 8; u++) a[u] = sv[cb + e + 16 + u];
-      KG_NRM2_STEP8(b, (unsigned)((mw >> (e + 8)) & 0xffULL))
-    }
-  }
-#undef KG_NRM2_STEP8
-  __builtin_amdgcn_wave_barrier();
-  return (m == 1) ? fabs(x[0]) : carry * sqrt(ssq);
-}
-
 }  // namespace
 
 // Dynamic LDS: [matrix region N*(N+1) doubles if lds_mats] + vectors.
@@ -520,15 +459,13 @@ __device__ double dnrm2_wave128(const double *x, int m, double *sv) {
 // Phase A: Householder tridiagonalisation (gsl_linalg_symmtd_decomp).
 // Outputs: Householder vectors H (row i = column i of A below the
 // diagonal), tau, diagonal d and sub-diagonal sd of the tridiagonal form.
-template <bool kLds>
-__global__ void __launch_bounds__(1024) k_tridiag(int N, const double *__restrict__ C, double *gA, double *gH,
-                                                  double *tauOut, double *dOut, double *sdOut,
-                                                  unsigned long long *trace) {
+__global__ void __launch_bounds__(1024) k_tridiag(int N, const double *__restrict__ C, double *gH, double *tauOut,
+                                                  double *dOut, double *sdOut, unsigned long long *trace) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wid = tid >> 6;
   const int lda = N + 1;
-  double *M = kLds ? smem : gA;
-  double *vb = kLds ? smem + (size_t)N * lda : smem;
+  double *M = smem;
+  double *vb = smem + (size_t)N * lda;
   double *x = vb, *scal = vb + N;
   double *sv = vb + N + 16;  // staged addends of a serial chain (wave 0); t2 of dsymv
   double *tv = sv + (N > 64 ? N : 64) + 8;  // tau * v_r, contiguous (dsymv); sv padded for dnrm2_wave
@@ -675,14 +612,13 @@ __global__ void __launch_bounds__(1024) k_tridiag(int N, const double *__restric
 
 // Phase B: Q = H_0 ... H_{N-3} (gsl_linalg_symmtd_unpack via
 // householder_hm), built transposed (Qt[col][row]) and stored to gQt.
-template <bool kLds>
 __global__ void __launch_bounds__(1024) k_unpack(int N, const double *__restrict__ gH,
                                                  const double *__restrict__ tau, double *gQt) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, nt = blockDim.x;
   const int lda = N + 1;
-  double *M = kLds ? smem : gQt;
-  double *h = kLds ? smem + (size_t)N * lda : smem;
+  double *M = smem;
+  double *h = smem + (size_t)N * lda;
   for (int idx = tid; idx < N * lda; idx += nt) {
     const int c = idx / lda, r = idx % lda;
     M[idx] = (r < N && c == r) ? 1.0 : 0.0;
@@ -710,8 +646,7 @@ __global__ void __launch_bounds__(1024) k_unpack(int N, const double *__restrict
     }
     __syncthreads();
   }
-  if (kLds)
-    for (int idx = tid; idx < N * lda; idx += nt) gQt[idx] = M[idx];
+  for (int idx = tid; idx < N * lda; idx += nt) gQt[idx] = M[idx];
 }
 
 // ------------------------------------------------------------------------
@@ -740,17 +675,14 @@ __host__ __device__ inline size_t tmw_lds_doubles(int N, int RW) {
 // rows per workgroup (<= 16): default spreads the rows over up to 256
 // workgroups (measured: more workgroups, fewer rows each, is faster — C2
 // 0.86 ms with 1 row vs 1.09 ms with 16; C4 7.4 ms with 2 vs 7.9 with 8);
-// KORALI_AMD_TMW_ROWS overrides
-int tmw_rows(int N) {
-  int rw = (N + 255) / 256;
-  if (const char *e = getenv("KORALI_AMD_TMW_ROWS")) rw = atoi(e);
-  if (rw < 1) rw = 1;
+// want >= 1 (KORALI_AMD_TMW_ROWS) overrides
+int tmw_rows(int N, int want) {
+  int rw = want >= 1 ? want : (N + 255) / 256;
   if (rw > 16) rw = 16;
   while (rw > 1 && tmw_lds_doubles(N, rw) * sizeof(double) > 150 * 1024) rw--;
   return rw;
 }
-int tmw_groups(int N) { return (N + tmw_rows(N) - 1) / tmw_rows(N); }
-size_t tmw_lds_bytes(int N) { return tmw_lds_doubles(N, tmw_rows(N)) * sizeof(double); }
+size_t tmw_lds_bytes(int N, int rows) { return tmw_lds_doubles(N, rows) * sizeof(double); }
 // comm buffer (u64 words): x granules [N][2N], pivot-row granules [N][2N],
 // abort word (+ pad to 16 bytes)
 size_t tmw_comm_words(int N) { return 4 * (size_t)N * N + 2; }
@@ -1020,1097 +952,6 @@ __global__ void __launch_bounds__(TMW_TPB) k_tridiag_mw(int N, const double *__r
   }
 }
 
-// ------------------------------------------------------------------------
-// Phase A in ONE workgroup for N <= 128 (the full symmetric matrix in LDS,
-// 132 KB at N = 128): no in-launch hand-offs at all.  Per Householder step i
-// (n = N-i-1), with the same operations in the same order as k_tridiag_mw:
-//   A  wave 0: dnrm2 of the pivot row, the Householder scalars (every lane
-//      redundantly, no broadcast), the scaled v / tau v and the outputs;
-//      waves 1..15 meanwhile finish the previous step's rank-2 update
-//   E  dsymv: waves 0-1 run the descending chains, waves 2-3 the ascending
-//      chains of rows i+1.., one SIMD each, products formed inline 8 ahead
-//   G  x_j = acc_j + tau t2_j and the xv products (all threads)
-//   I  wave 0: the xv chain, alpha
-//   K  x += alpha v
-//   M  rank-2 update of the trailing block: wave 0 updates the next pivot
-//      row first and goes straight on to the next step's dnrm2 while waves
-//      1..15 update rows i+2.. (the column below the pivot is never read
-//      again and is skipped).  Its element formula needs no case split:
-//        m[a][b] += (-v_a) x_b + (-x_a) v_b   (a >= b, dsyr2 Lower)
-//      has the same two rounded products as (-v_b) x_a + (-x_b) v_a, so both
-//      triangles get fl(m + fl(fl(-v_r x_c) + fl(-x_r v_c))) for row r.
-// v is double-buffered across steps because A of step i+1 (wave 0) writes it
-// while the rank-2 update of step i still reads it.
-constexpr int T1_TPB = 1024;
-__host__ __device__ inline size_t t1_lds_doubles(int N) {
-  return (size_t)N * (N + 1) + 2 * (128 + (size_t)(N + 32)) + (N + 64) + 3 * (size_t)(N + 32) + 16 + 8;
-}
-bool t1_fits(int N) { return N >= 3 && N <= 128 && t1_lds_doubles(N) * sizeof(double) <= 160 * 1024; }
-
-// acc = 0 + sum_{t < T} a[S t] b[S t] (S = -1 descending, +1 ascending), T
-// wave-uniform; products of the next 8 formed while the current 8 are added,
-// p / q swapping roles.  Callers align every lane's own chain to the end of
-// the T steps: its leading steps read zero-padded operands (0 x finite =
-// +-0.0, and a sum that starts at +0.0 is unchanged by adding +-0.0 under
-// round-to-nearest), so no lane needs a mask.
-template <int S>
-__device__ __forceinline__ double padded_chain(const double *a, const double *b, int T_) {
-  const int T = __builtin_amdgcn_readfirstlane(T_);
-  double acc = 0.0;
-  int t = 0;
-  if (T >= 8) {
-    double p[8], q[8];
-#pragma unroll
-    for (int u = 0; u < 8; u++) p[u] = a[S * u] * b[S * u];
-    t = 8;
-    for (; t + 16 <= T; t += 16) {
-      const double *at = a + S * t, *bt = b + S * t;
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        q[u] = at[S * u] * bt[S * u];
-        acc += p[u];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        p[u] = at[S * (8 + u)] * bt[S * (8 + u)];
-        acc += q[u];
-      }
-    }
-    if (t + 8 <= T) {
-      const double *at = a + S * t, *bt = b + S * t;
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        q[u] = at[S * u] * bt[S * u];
-        acc += p[u];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++) p[u] = q[u];
-      t += 8;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += p[u];
-  }
-  for (; t < T; t++) acc += a[S * t] * b[S * t];
-  return acc;
-}
-
-__global__ void __launch_bounds__(T1_TPB) k_tridiag_1wg(int N, const double *__restrict__ C, double *gH,
-                                                        double *tauOut, double *dOut, double *sdOut,
-                                                        unsigned long long *trace, int xflags) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nt = blockDim.x;
-  const int lda = N + 1, VS = N + 32;
-  double *M = smem;                    // row r at r*lda; column N is a zero pad
-  double *vbuf = M + (size_t)N * lda;  // v (v_0 = 1), two buffers (step parity),
-                                       // each after 128 zeros
-  double *tv = vbuf + 2 * (128 + VS);  // tau v, zeros from index n to n+63
-  double *xl = tv + (N + 64);          // x
-  double *t2b = xl + VS;               // ascending dsymv chains
-  double *sv = t2b + VS;               // dnrm2 addends, then the xv products
-  double *scal = sv + VS;              // 16 scalars
-  unsigned long long *msk = (unsigned long long *)(scal + 16);  // dnrm2 rescale masks
-  const bool tr = trace && tid == 0;
-  unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tm = tr ? __builtin_amdgcn_s_memtime() : 0;
-  if ((xflags & 1) && wid == 0) __builtin_amdgcn_s_setprio(3);
-  if ((xflags & 4) && wid > 0 && wid < 4) __builtin_amdgcn_s_setprio(2);
-#define T1_MARK(k)                                                \
-  if (tr) {                                                       \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();   \
-    tacc[k] += t_ - tm;                                           \
-    tm = t_;                                                      \
-  }
-  // zero everything first: the padded dsymv chains read the pad column, the
-  // zeros around v / tau v and (past row N-1) the vectors, all finite
-  for (size_t idx = tid; idx < t1_lds_doubles(N); idx += nt) smem[idx] = 0.0;
-  __syncthreads();
-  for (int idx = tid; idx < N * N; idx += nt) {
-    const int r = idx / N, c = idx % N;
-    M[(size_t)r * lda + c] = (c <= r) ? C[(size_t)r * N + c] : C[(size_t)c * N + r];
-  }
-  __syncthreads();
-  for (int i = 0; i + 2 < N; i++) {
-    const int n = N - i - 1;
-    double *vloc = vbuf + 128 + (i & 1) * (128 + VS);
-    // ---- A: Householder vector of pivot row i (wave 0; every lane holds the scalars)
-    if (wid == 0) {
-      const double *v = M + (size_t)i * lda + i + 1;  // v[0] = alpha, v[1..n-1]
-      const double xnorm = dnrm2_wave128(v + 1, n - 1, sv);
-      if (tr) {
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-        tacc[6] += t_ - tm;
-        tm = t_;
-      }
-      double tau_i = 0.0, f1 = 1.0, f2 = 1.0, beta = 0.0;
-      int branch = 0;
-      if (xnorm != 0) {
-        const double alpha = v[0];
-        beta = -(alpha >= 0.0 ? 1.0 : -1.0) * hypot_fdlibm(alpha, xnorm);
-        tau_i = (beta - alpha) / beta;
-        const double sgap = alpha - beta;
-        if (fabs(sgap) > DMIN) {
-          f1 = 1.0 / sgap;
-          branch = 1;
-        } else {
-          f1 = EPS / sgap;
-          f2 = 1.0 / EPS;
-          branch = 2;
-        }
-      }
-      const double v0out = branch ? beta : v[0];
-      if (tr) {
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-        tacc[7] += t_ - tm;
-        tm = t_;
-      }
-      for (int r = lane; r < n; r += 64) {
-        double t = v[r];
-        if (r > 0 && branch != 0) {
-          t = t * f1;
-          if (branch == 2) t = t * f2;
-        }
-        gH[(size_t)i * N + r] = (r == 0) ? v0out : t;
-        const double vr = (r == 0) ? 1.0 : t;
-        vloc[r] = vr;
-        tv[r] = tau_i * vr;
-      }
-      tv[n + lane] = 0.0;  // the descending chains' leading pad
-      if (lane == 0) {
-        scal[0] = tau_i;
-        tauOut[i] = tau_i;
-        sdOut[i] = v0out;
-      }
-    }
-    T1_MARK(0)
-    __syncthreads();
-    T1_MARK(1)
-    const double tau_i = scal[0];
-    if (tau_i == 0.0) continue;  // no update this step (uniform)
-    // ---- E: dsymv chains of rows r = i+1+j, every lane's chain aligned to
-    // the end of its wave's T steps (leading steps read the zero pads)
-    if (wid < 4) {
-      const unsigned long long te0 = (trace && lane == 0) ? __builtin_amdgcn_s_memtime() : 0;
-      const int j = lane + 64 * (wid & 1);
-      const int r = i + 1 + (j < n ? j : n - 1);
-      const double *row = M + (size_t)r * lda;
-      const int lo = 64 * (wid & 1);                     // smallest j of this wave
-      const int hi = min(n, lo + 64) - 1;                // largest active j
-      if (wid < 2) {  // c = N-1 .. r+1 descending (n-1-j terms), then the diagonal
-        const int sh = j - lo;
-        const double acc = padded_chain<-1>(tv + (n - 1) + sh, row + (N - 1) + sh, n - 1 - lo);
-        if (j < n) xl[j] = acc + tv[j] * row[r];
-      } else {  // c = i+1 .. r-1 ascending (j terms)
-        const int sh = j - hi;
-        const double acc = padded_chain<1>(vloc + sh, row + i + 1 + sh, hi);
-        if (j < n) t2b[j] = acc;
-      }
-      if (trace && lane == 0 && (wid == 0 || wid == 3)) {
-        __builtin_amdgcn_s_waitcnt(0);
-        trace[wid == 0 ? 14 : 15] += __builtin_amdgcn_s_memtime() - te0;  // one writer per slot
-      }
-    }
-    __syncthreads();
-    T1_MARK(2)
-    // ---- G, I, K on wave 0 alone (two elements per lane, no block barriers):
-    // x = acc + tau t2 and the xv products, the xv chain, alpha = -(tau/2) xv,
-    // x += alpha v
-    if (wid == 0) {
-      for (int r = lane; r < n; r += 64) {
-        const double x = xl[r] + tau_i * t2b[r];
-        xl[r] = x;
-        sv[r] = x * vloc[r];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const double alpha = -(tau_i / 2.0) * staged_chain(0.0, sv, n);
-      T1_MARK(3)
-      for (int r = lane; r < n; r += 64) xl[r] += alpha * vloc[r];
-    }
-    __syncthreads();
-    T1_MARK(4)
-    // ---- M: rank-2 update (both triangles), next pivot row first on wave 0
-    if (wid == 0) {
-      double *row = M + (size_t)(i + 1) * lda + i + 1;
-      const double x0 = xl[0], v0 = vloc[0];
-      for (int jj = lane; jj < n; jj += 64) {
-        const double tmp1 = -1.0 * vloc[jj], tmp2 = -1.0 * xl[jj];
-        row[jj] += tmp1 * x0 + tmp2 * v0;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else if (n > 1) {
-      // lane's columns jj = 1 + lane, 65 + lane (n <= 128)
-      const int ja = 1 + lane, jb = 65 + lane;
-      const double xa = ja < n ? xl[ja] : 0.0, va = ja < n ? vloc[ja] : 0.0;
-      const double xb = jb < n ? xl[jb] : 0.0, vb = jb < n ? vloc[jb] : 0.0;
-      for (int jr = wid; jr < n; jr += 15) {
-        double *row = M + (size_t)(i + 1 + jr) * lda + i + 1;
-        const double nvr = -1.0 * vloc[jr], nxr = -1.0 * xl[jr];
-        if (ja < n) row[ja] += nvr * xa + nxr * va;
-        if (jb < n) row[jb] += nvr * xb + nxr * vb;
-      }
-    }
-    T1_MARK(5)
-  }
-  __syncthreads();
-#undef T1_MARK
-  if (tr) {
-    for (int k = 0; k < 6; k++) trace[8 + k] += tacc[k];
-    trace[29] += tacc[6];
-    trace[30] += tacc[7];
-  }
-  for (int r = tid; r < N; r += nt) {
-    dOut[r] = M[(size_t)r * lda + r];
-    if (r == N - 2) sdOut[r] = M[(size_t)r * lda + r + 1];
-  }
-}
-
-// ------------------------------------------------------------------------
-// Phase A in ONE workgroup, version 2 (the default for N <= 128): the
-// trailing block is stored as its STRICTLY UPPER triangle (zeros on and
-// below the diagonal; the diagonal lives in its own vector).  Then every
-// gslcblas dsymv chain walks a zero-padded sequence without any lane mask:
-//   descending (rows r, lockstep over columns c = N-1, N-2, ...):
-//     acc_r += tv_c M[r][c]   — M[r][c] = 0 for c <= r adds +-0.0 to an
-//     accumulator that started at +0.0 and so is never -0.0: unchanged
-//   ascending (c = i+1, i+2, ...): t2_r += v_c M[c][r]  (M[c][r] = m[r][c]
-//     for c < r by symmetry, 0 for c >= r)
-// and the rank-2 update touches only the upper triangle and the diagonal
-// (half of the full symmetric update).  Both chain reads are conflict-free
-// (a column walk over rows of stride N+1, a row walk over consecutive r);
-// the vector operand is a broadcast.  dnrm2's ssq chain takes its rare
-// rescaling steps (a new running maximum) through scalar branches, so the
-// common step is one dependent add.  Operation order is the reference's
-// throughout, so the result is bit-identical to
-// k_tridiag_1wg and the oracle.
-constexpr int T2_TPB = 1024, T2_VP = 16;  // T2_VP: pad before / after each vector (chain read-ahead)
-__host__ __device__ inline size_t t2_vec(int N) { return (size_t)N + 2 * T2_VP; }
-__host__ __device__ inline size_t t2_lds_doubles(int N) {
-  // M | dg | vA[2] | tvA[2] | xA[2] | xd | t2 | sv (192) | scal
-  return (size_t)N * (N + 1) + 9 * t2_vec(N) + 192 + 16;
-}
-bool t2_fits(int N) { return N >= 3 && N <= 128 && t2_lds_doubles(N) * sizeof(double) <= 160 * 1024; }
-
-// s_waitcnt lgkmcnt(K) alone (vmcnt / expcnt left at their maxima).  An
-// explicit wait satisfies the compiler's own wait insertion for every LDS
-// load it covers, so a batch of adds that follows waits once, not per
-// value (a wait per dependent add costs ~4 cycles of the ~8 of the add).
-#define KG_WAIT_LGKM(K) __builtin_amdgcn_s_waitcnt(0xC07F | ((K) << 8))
-
-// acc = 0 + sum_{t < T} w[S t] m[S t ms] in order (T wave-uniform); the next
-// 8 steps' operands are read while the current 8 are multiplied and added
-// (two register sets, roles alternating).  Scheduling barriers keep the
-// read-ahead where it is written and one explicit wait per batch replaces
-// the compiler's wait per operand (KG_WAIT_LGKM: the compiler still adds a
-// wait for anything the explicit one does not cover, so the count only
-// tunes speed, never correctness).  Reads run at most 8 steps past T (in
-// bounds by the LDS layout) and are not added.
-#define KG_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-template <int S>
-__device__ __forceinline__ double lockstep_chain(const double *w, const double *m, int ms, int T_) {
-  const int T = __builtin_amdgcn_readfirstlane(T_);
-  double acc = 0.0;
-  double wa[8], ma[8], wb[8], mb[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    wa[u] = w[S * u];
-    ma[u] = m[S * u * ms];
-  }
-  int t = 0;
-  for (; t + 16 <= T; t += 16) {
-    const double *wt = w + S * (t + 8), *mt = m + S * (t + 8) * ms;
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      wb[u] = wt[S * u];
-      mb[u] = mt[S * u * ms];
-    }
-    KG_SCHED_FENCE();
-    KG_WAIT_LGKM(12);
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += wa[u] * ma[u];
-    KG_SCHED_FENCE();
-    wt = w + S * (t + 16);
-    mt = m + S * (t + 16) * ms;
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      wa[u] = wt[S * u];
-      ma[u] = mt[S * u * ms];
-    }
-    KG_SCHED_FENCE();
-    KG_WAIT_LGKM(12);
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += wb[u] * mb[u];
-    KG_SCHED_FENCE();
-  }
-  if (t + 8 <= T) {
-    const double *wt = w + S * (t + 8), *mt = m + S * (t + 8) * ms;
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      wb[u] = wt[S * u];
-      mb[u] = mt[S * u * ms];
-    }
-    KG_SCHED_FENCE();
-    KG_WAIT_LGKM(12);
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += wa[u] * ma[u];
-    t += 8;
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (t + u < T) acc += wb[u] * mb[u];
-  } else {
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (t + u < T) acc += wa[u] * ma[u];
-  }
-  return acc;
-}
-
-// ordered add-only chain acc + x_0 + ... + x_{cnt-1} over values held one
-// per lane (x_e in lane e of v0 for e < 64, of v1 for e >= 64; cnt <= 128),
-// each read into scalar registers with v_readlane (no LDS traffic); every
-// lane returns the sum
-__device__ __forceinline__ double lane_sum(double acc, double v0, double v1, int cnt_) {
-  const int cnt = __builtin_amdgcn_readfirstlane(cnt_);
-  const long long b0 = __double_as_longlong(v0), b1 = __double_as_longlong(v1);
-  const int l0 = (int)b0, h0 = (int)(b0 >> 32), l1 = (int)b1, h1 = (int)(b1 >> 32);
-#define KG_LANE_STEP(L, H, E)                                                                        \
-  acc += __longlong_as_double(((long long)__builtin_amdgcn_readlane(H, E) << 32) |                    \
-                              (unsigned int)__builtin_amdgcn_readlane(L, E))
-  int e = 0;
-  for (; e + 8 <= min(cnt, 64); e += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) KG_LANE_STEP(l0, h0, e + u);
-  }
-  for (; e < min(cnt, 64); e++) KG_LANE_STEP(l0, h0, e);
-  for (; e + 8 <= cnt; e += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) KG_LANE_STEP(l1, h1, e - 64 + u);
-  }
-  for (; e < cnt; e++) KG_LANE_STEP(l1, h1, e - 64);
-#undef KG_LANE_STEP
-  return acc;
-}
-
-
-// staged_sum reading pairs with 16-byte LDS loads (p 16-byte aligned): the
-// next 8 values are in flight (4 loads) while the current 8 are added after
-// ONE wait
-__device__ __forceinline__ double staged_sum_v2(double acc, const double *p, int cnt_) {
-  const int cnt = __builtin_amdgcn_readfirstlane(cnt_);
-  const double2 *q2 = (const double2 *)p;
-  double2 a[4], b[4];
-#pragma unroll
-  for (int u = 0; u < 4; u++) a[u] = q2[u];
-  int q = 0;
-  for (; q + 16 <= cnt; q += 16) {
-#pragma unroll
-    for (int u = 0; u < 4; u++) b[u] = q2[(q >> 1) + 4 + u];
-    KG_WAIT_LGKM(4);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      acc += a[u].x;
-      acc += a[u].y;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) a[u] = q2[(q >> 1) + 8 + u];
-    KG_WAIT_LGKM(4);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      acc += b[u].x;
-      acc += b[u].y;
-    }
-  }
-  if (q + 8 <= cnt) {
-#pragma unroll
-    for (int u = 0; u < 4; u++) b[u] = q2[(q >> 1) + 4 + u];
-    KG_WAIT_LGKM(4);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      acc += a[u].x;
-      acc += a[u].y;
-    }
-    q += 8;
-    KG_WAIT_LGKM(0);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      if (q + 2 * u < cnt) acc += b[u].x;
-      if (q + 2 * u + 1 < cnt) acc += b[u].y;
-    }
-  } else {
-    KG_WAIT_LGKM(0);
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      if (q + 2 * u < cnt) acc += a[u].x;
-      if (q + 2 * u + 1 < cnt) acc += a[u].y;
-    }
-  }
-  return acc;
-}
-
-// acc + p[0] + ... + p[cnt-1] (p an LDS address, wave-uniform; 0 <= cnt
-// <= 128) as ONE straight-line inline-assembly sequence: the next 8 values
-// are in flight (8 ds_read_b64) while the current 8 are added after a
-// single counted wait; the only branches are forward exits to the tail.
-// (Compiled code waits before every add and hoists the loads next to their
-// uses, ~15 cycles per element; a dependent FP64 add is 8.3, an LDS-fed
-// add chain waiting once per 8 values 10.6 — tools/ubench_issue.hip.)
-// Reads run up to 16 values past cnt (callers pad) and are not added.
-__device__ __forceinline__ double lds_chain_add(double acc, const double *p, int cnt) {
-  const unsigned va = (unsigned)(size_t)(const __attribute__((address_space(3))) double *)p;
-  int rem = __builtin_amdgcn_readfirstlane(cnt);
-  double a[8], b[8];
-  asm volatile(
-"ds_read_b64 %[a0], %[va] offset:0\n"
-"ds_read_b64 %[a1], %[va] offset:8\n"
-"ds_read_b64 %[a2], %[va] offset:16\n"
-"ds_read_b64 %[a3], %[va] offset:24\n"
-"ds_read_b64 %[a4], %[va] offset:32\n"
-"ds_read_b64 %[a5], %[va] offset:40\n"
-"ds_read_b64 %[a6], %[va] offset:48\n"
-"ds_read_b64 %[a7], %[va] offset:56\n"
-"ds_read_b64 %[b0], %[va] offset:64\n"
-"ds_read_b64 %[b1], %[va] offset:72\n"
-"ds_read_b64 %[b2], %[va] offset:80\n"
-"ds_read_b64 %[b3], %[va] offset:88\n"
-"ds_read_b64 %[b4], %[va] offset:96\n"
-"ds_read_b64 %[b5], %[va] offset:104\n"
-"ds_read_b64 %[b6], %[va] offset:112\n"
-"ds_read_b64 %[b7], %[va] offset:120\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:128\n"
-"ds_read_b64 %[a1], %[va] offset:136\n"
-"ds_read_b64 %[a2], %[va] offset:144\n"
-"ds_read_b64 %[a3], %[va] offset:152\n"
-"ds_read_b64 %[a4], %[va] offset:160\n"
-"ds_read_b64 %[a5], %[va] offset:168\n"
-"ds_read_b64 %[a6], %[va] offset:176\n"
-"ds_read_b64 %[a7], %[va] offset:184\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:192\n"
-"ds_read_b64 %[b1], %[va] offset:200\n"
-"ds_read_b64 %[b2], %[va] offset:208\n"
-"ds_read_b64 %[b3], %[va] offset:216\n"
-"ds_read_b64 %[b4], %[va] offset:224\n"
-"ds_read_b64 %[b5], %[va] offset:232\n"
-"ds_read_b64 %[b6], %[va] offset:240\n"
-"ds_read_b64 %[b7], %[va] offset:248\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:256\n"
-"ds_read_b64 %[a1], %[va] offset:264\n"
-"ds_read_b64 %[a2], %[va] offset:272\n"
-"ds_read_b64 %[a3], %[va] offset:280\n"
-"ds_read_b64 %[a4], %[va] offset:288\n"
-"ds_read_b64 %[a5], %[va] offset:296\n"
-"ds_read_b64 %[a6], %[va] offset:304\n"
-"ds_read_b64 %[a7], %[va] offset:312\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:320\n"
-"ds_read_b64 %[b1], %[va] offset:328\n"
-"ds_read_b64 %[b2], %[va] offset:336\n"
-"ds_read_b64 %[b3], %[va] offset:344\n"
-"ds_read_b64 %[b4], %[va] offset:352\n"
-"ds_read_b64 %[b5], %[va] offset:360\n"
-"ds_read_b64 %[b6], %[va] offset:368\n"
-"ds_read_b64 %[b7], %[va] offset:376\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:384\n"
-"ds_read_b64 %[a1], %[va] offset:392\n"
-"ds_read_b64 %[a2], %[va] offset:400\n"
-"ds_read_b64 %[a3], %[va] offset:408\n"
-"ds_read_b64 %[a4], %[va] offset:416\n"
-"ds_read_b64 %[a5], %[va] offset:424\n"
-"ds_read_b64 %[a6], %[va] offset:432\n"
-"ds_read_b64 %[a7], %[va] offset:440\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:448\n"
-"ds_read_b64 %[b1], %[va] offset:456\n"
-"ds_read_b64 %[b2], %[va] offset:464\n"
-"ds_read_b64 %[b3], %[va] offset:472\n"
-"ds_read_b64 %[b4], %[va] offset:480\n"
-"ds_read_b64 %[b5], %[va] offset:488\n"
-"ds_read_b64 %[b6], %[va] offset:496\n"
-"ds_read_b64 %[b7], %[va] offset:504\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:512\n"
-"ds_read_b64 %[a1], %[va] offset:520\n"
-"ds_read_b64 %[a2], %[va] offset:528\n"
-"ds_read_b64 %[a3], %[va] offset:536\n"
-"ds_read_b64 %[a4], %[va] offset:544\n"
-"ds_read_b64 %[a5], %[va] offset:552\n"
-"ds_read_b64 %[a6], %[va] offset:560\n"
-"ds_read_b64 %[a7], %[va] offset:568\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:576\n"
-"ds_read_b64 %[b1], %[va] offset:584\n"
-"ds_read_b64 %[b2], %[va] offset:592\n"
-"ds_read_b64 %[b3], %[va] offset:600\n"
-"ds_read_b64 %[b4], %[va] offset:608\n"
-"ds_read_b64 %[b5], %[va] offset:616\n"
-"ds_read_b64 %[b6], %[va] offset:624\n"
-"ds_read_b64 %[b7], %[va] offset:632\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:640\n"
-"ds_read_b64 %[a1], %[va] offset:648\n"
-"ds_read_b64 %[a2], %[va] offset:656\n"
-"ds_read_b64 %[a3], %[va] offset:664\n"
-"ds_read_b64 %[a4], %[va] offset:672\n"
-"ds_read_b64 %[a5], %[va] offset:680\n"
-"ds_read_b64 %[a6], %[va] offset:688\n"
-"ds_read_b64 %[a7], %[va] offset:696\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:704\n"
-"ds_read_b64 %[b1], %[va] offset:712\n"
-"ds_read_b64 %[b2], %[va] offset:720\n"
-"ds_read_b64 %[b3], %[va] offset:728\n"
-"ds_read_b64 %[b4], %[va] offset:736\n"
-"ds_read_b64 %[b5], %[va] offset:744\n"
-"ds_read_b64 %[b6], %[va] offset:752\n"
-"ds_read_b64 %[b7], %[va] offset:760\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:768\n"
-"ds_read_b64 %[a1], %[va] offset:776\n"
-"ds_read_b64 %[a2], %[va] offset:784\n"
-"ds_read_b64 %[a3], %[va] offset:792\n"
-"ds_read_b64 %[a4], %[va] offset:800\n"
-"ds_read_b64 %[a5], %[va] offset:808\n"
-"ds_read_b64 %[a6], %[va] offset:816\n"
-"ds_read_b64 %[a7], %[va] offset:824\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:832\n"
-"ds_read_b64 %[b1], %[va] offset:840\n"
-"ds_read_b64 %[b2], %[va] offset:848\n"
-"ds_read_b64 %[b3], %[va] offset:856\n"
-"ds_read_b64 %[b4], %[va] offset:864\n"
-"ds_read_b64 %[b5], %[va] offset:872\n"
-"ds_read_b64 %[b6], %[va] offset:880\n"
-"ds_read_b64 %[b7], %[va] offset:888\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:896\n"
-"ds_read_b64 %[a1], %[va] offset:904\n"
-"ds_read_b64 %[a2], %[va] offset:912\n"
-"ds_read_b64 %[a3], %[va] offset:920\n"
-"ds_read_b64 %[a4], %[va] offset:928\n"
-"ds_read_b64 %[a5], %[va] offset:936\n"
-"ds_read_b64 %[a6], %[va] offset:944\n"
-"ds_read_b64 %[a7], %[va] offset:952\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[b0], %[va] offset:960\n"
-"ds_read_b64 %[b1], %[va] offset:968\n"
-"ds_read_b64 %[b2], %[va] offset:976\n"
-"ds_read_b64 %[b3], %[va] offset:984\n"
-"ds_read_b64 %[b4], %[va] offset:992\n"
-"ds_read_b64 %[b5], %[va] offset:1000\n"
-"ds_read_b64 %[b6], %[va] offset:1008\n"
-"ds_read_b64 %[b7], %[va] offset:1016\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 2f\n"
-"v_add_f64 %[acc], %[acc], %[a0]\n"
-"v_add_f64 %[acc], %[acc], %[a1]\n"
-"v_add_f64 %[acc], %[acc], %[a2]\n"
-"v_add_f64 %[acc], %[acc], %[a3]\n"
-"v_add_f64 %[acc], %[acc], %[a4]\n"
-"v_add_f64 %[acc], %[acc], %[a5]\n"
-"v_add_f64 %[acc], %[acc], %[a6]\n"
-"v_add_f64 %[acc], %[acc], %[a7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"ds_read_b64 %[a0], %[va] offset:1024\n"
-"ds_read_b64 %[a1], %[va] offset:1032\n"
-"ds_read_b64 %[a2], %[va] offset:1040\n"
-"ds_read_b64 %[a3], %[va] offset:1048\n"
-"ds_read_b64 %[a4], %[va] offset:1056\n"
-"ds_read_b64 %[a5], %[va] offset:1064\n"
-"ds_read_b64 %[a6], %[va] offset:1072\n"
-"ds_read_b64 %[a7], %[va] offset:1080\n"
-"s_waitcnt lgkmcnt(8)\n s_cmp_lt_i32 %[rem], 8\n s_cbranch_scc1 3f\n"
-"v_add_f64 %[acc], %[acc], %[b0]\n"
-"v_add_f64 %[acc], %[acc], %[b1]\n"
-"v_add_f64 %[acc], %[acc], %[b2]\n"
-"v_add_f64 %[acc], %[acc], %[b3]\n"
-"v_add_f64 %[acc], %[acc], %[b4]\n"
-"v_add_f64 %[acc], %[acc], %[b5]\n"
-"v_add_f64 %[acc], %[acc], %[b6]\n"
-"v_add_f64 %[acc], %[acc], %[b7]\n"
-"s_sub_i32 %[rem], %[rem], 8\n"
-"s_branch 9f\n"
-"2:\n"
-"s_cmp_lt_i32 %[rem], 1\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a0]\n"
-"s_cmp_lt_i32 %[rem], 2\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a1]\n"
-"s_cmp_lt_i32 %[rem], 3\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a2]\n"
-"s_cmp_lt_i32 %[rem], 4\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a3]\n"
-"s_cmp_lt_i32 %[rem], 5\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a4]\n"
-"s_cmp_lt_i32 %[rem], 6\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a5]\n"
-"s_cmp_lt_i32 %[rem], 7\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[a6]\n"
-"s_branch 9f\n"
-"3:\n"
-"s_cmp_lt_i32 %[rem], 1\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b0]\n"
-"s_cmp_lt_i32 %[rem], 2\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b1]\n"
-"s_cmp_lt_i32 %[rem], 3\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b2]\n"
-"s_cmp_lt_i32 %[rem], 4\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b3]\n"
-"s_cmp_lt_i32 %[rem], 5\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b4]\n"
-"s_cmp_lt_i32 %[rem], 6\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b5]\n"
-"s_cmp_lt_i32 %[rem], 7\n s_cbranch_scc1 9f\n v_add_f64 %[acc], %[acc], %[b6]\n"
-"9:\n s_waitcnt lgkmcnt(0)\n"
-      : [acc] "+&v"(acc), [rem] "+&s"(rem), [a0] "=&v"(a[0]), [a1] "=&v"(a[1]), [a2] "=&v"(a[2]), [a3] "=&v"(a[3]), [a4] "=&v"(a[4]), [a5] "=&v"(a[5]), [a6] "=&v"(a[6]), [a7] "=&v"(a[7]), [b0] "=&v"(b[0]), [b1] "=&v"(b[1]), [b2] "=&v"(b[2]), [b3] "=&v"(b[3]), [b4] "=&v"(b[4]), [b5] "=&v"(b[5]), [b6] "=&v"(b[6]), [b7] "=&v"(b[7])
-      : [va] "v"(va)
-      : "scc", "memory");
-  return acc;
-}
-
-// staged_sum with the loads 16 ahead: three register sets of 8 rotate
-// (a wait covers only the batch it consumes); reads up to 24 past cnt
-__device__ __forceinline__ double staged_sum3(double acc, const double *p, int cnt_) {
-  const int cnt = __builtin_amdgcn_readfirstlane(cnt_);
-  double a[8], b[8], c[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) {
-    a[u] = p[u];
-    b[u] = p[8 + u];
-  }
-  int q = 0;
-  for (; q + 24 <= cnt; q += 24) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) c[u] = p[q + 16 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += a[u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) a[u] = p[q + 24 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += b[u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) b[u] = p[q + 32 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += c[u];
-  }
-  // tail: fewer than 24 left; a holds q..q+7, b holds q+8..q+15
-#pragma unroll
-  for (int u = 0; u < 8; u++)
-    if (q + u < cnt) acc += a[u];
-#pragma unroll
-  for (int u = 0; u < 8; u++)
-    if (q + 8 + u < cnt) acc += b[u];
-  if (q + 16 < cnt) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) c[u] = p[q + 16 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (q + 16 + u < cnt) acc += c[u];
-  }
-  return acc;
-}
-
-// ordered add-only chain acc + p[0] + ... + p[cnt-1] over LDS values, 8
-// loaded ahead (reads up to 8 past cnt, not added)
-__device__ __forceinline__ double staged_sum(double acc, const double *p, int cnt_) {
-  const int cnt = __builtin_amdgcn_readfirstlane(cnt_);
-  double a[8], b[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) a[u] = p[u];
-  int q = 0;
-  for (; q + 16 <= cnt; q += 16) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) b[u] = p[q + 8 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += a[u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) a[u] = p[q + 16 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += b[u];
-  }
-  if (q + 8 <= cnt) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) b[u] = p[q + 8 + u];
-#pragma unroll
-    for (int u = 0; u < 8; u++) acc += a[u];
-    q += 8;
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (q + u < cnt) acc += b[u];
-  } else {
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-      if (q + u < cnt) acc += a[u];
-  }
-  return acc;
-}
-
-// rescale flags of the 8 addends e .. e+7 (e a multiple of 8)
-__device__ __forceinline__ unsigned nrm2_bits(unsigned long long k0, unsigned long long k1, int e) {
-  return (unsigned)(((e < 64) ? (k0 >> e) : (k1 >> (e - 64))) & 0xffULL);
-}
-// 8 steps of dnrm2's ssq recurrence: ssq += t (plain) or ssq = 1 + ssq t t
-// (a new running maximum, rare: taken through scalar branches so the plain
-// step stays one dependent add)
-__device__ __forceinline__ double nrm2_batch(double ssq, const double (&t)[8], unsigned bits) {
-  if (bits == 0u) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) ssq += t[u];
-  } else {
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-      if ((bits >> u) & 1u) {
-        __asm__ volatile("" ::: "memory");
-        ssq = 1.0 + ssq * t[u] * t[u];
-      } else {
-        ssq += t[u];
-      }
-    }
-  }
-  return ssq;
-}
-
-// gslcblas dnrm2 of m <= 128 elements held in registers (element e = lane in
-// x0, e = 64 + lane in x1; only e < m are read), by one wave; every lane
-// returns the result.  Addends staged in sv (m rounded up to 8, zero-padded:
-// +0.0 leaves ssq >= 1 unchanged).
-__device__ double dnrm2_regs(double x0, double x1, int m, double *sv, bool tr, unsigned long long *tacc,
-                             unsigned long long &tm) {
-  const int lane = threadIdx.x & 63;
-  const int m8 = (m + 7) & ~7;
-  const int e0 = lane, e1 = lane + 64;
-  const double a0 = e0 < m ? fabs(x0) : 0.0, a1 = e1 < m ? fabs(x1) : 0.0;
-  double pm0, pm1;
-  wave_prefix_max2_nonneg(a0, a1, pm0, pm1);
-  const double c0 = readlane_d(pm0, 63);
-  const double b0 = dpp_d<0x138, 0xf>(pm0);            // running max before e0 (lane 0: 0.0)
-  const double b1 = fmax(dpp_d<0x138, 0xf>(pm1), c0);  // before e1
-  const bool z0 = a0 != 0.0, z1 = a1 != 0.0;           // zero elements are skipped by dnrm2
-  const bool n0 = z0 && b0 < a0, n1 = z1 && b1 < a1;   // a new running maximum
-  // one division per element, operands selected (zeros: 0 / 1), no branches
-  const double q0 = (z0 ? (n0 ? b0 : a0) : 0.0) / (z0 ? (n0 ? a0 : b0) : 1.0);
-  const double q1 = (z1 ? (n1 ? b1 : a1) : 0.0) / (z1 ? (n1 ? a1 : b1) : 1.0);
-  const unsigned long long k0 = __ballot(n0), k1 = __ballot(n1);
-  sv[e0] = n0 ? q0 : q0 * q0;  // e >= m: q = 0 (sv holds 192 doubles)
-  sv[e1] = n1 ? q1 : q1 * q1;
-  const double carry = fmax(c0, readlane_d(pm1, 63));
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (tr) {
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();
-    tacc[0] += t_ - tm;
-    tm = t_;
-  }
-  // the ssq recurrence in the reference's order: batches of 8 addends, the
-  // next batch loaded while the current one is added (two register sets,
-  // roles alternating: a wait covers only the batch it consumes)
-  double ssq = 1.0;
-  double a[8], b[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) a[u] = sv[u];
-  for (int e = 0; e < m8; e += 16) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) b[u] = sv[e + 8 + u];  // sv has 64 doubles of slack
-    ssq = nrm2_batch(ssq, a, nrm2_bits(k0, k1, e));
-    if (e + 8 >= m8) break;
-#pragma unroll
-    for (int u = 0; u < 8; u++) a[u] = sv[e + 16 + u];
-    ssq = nrm2_batch(ssq, b, nrm2_bits(k0, k1, e + 8));
-  }
-  __builtin_amdgcn_wave_barrier();
-  return (m == 1) ? fabs(x0) : carry * sqrt(ssq);
-}
-
-__global__ void __launch_bounds__(T2_TPB) k_tridiag_1wg2(int N, const double *__restrict__ C, double *gH,
-                                                         double *tauOut, double *dOut, double *sdOut,
-                                                         unsigned long long *trace) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nt = blockDim.x;
-  const int lda = N + 1, VS = (int)t2_vec(N);
-  double *M = smem;                       // strictly upper triangle, row r at r*lda
-  double *dg = M + (size_t)N * lda + T2_VP;  // diagonal
-  double *vbase = dg - T2_VP + VS;        // vA[2], tvA[2], xA[2]: absolute column index
-  auto vA = [&](int p) { return vbase + (size_t)p * VS + T2_VP; };
-  auto tvA = [&](int p) { return vbase + (size_t)(2 + p) * VS + T2_VP; };
-  auto xA = [&](int p) { return vbase + (size_t)(4 + p) * VS + T2_VP; };
-  double *xd = vbase + (size_t)6 * VS + T2_VP;  // descending chain + diagonal term, by j
-  double *t2 = xd + VS;                          // ascending chain, by j
-  double *sv = t2 + VS - T2_VP;                  // 192: dnrm2 addends, then the xv products
-  double *scal = sv + 192;                       // 16 scalars
-  const bool tr = trace && tid == 0;
-  unsigned long long tacc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tm = tr ? __builtin_amdgcn_s_memtime() : 0;
-#define T2_MARK(k)                                                \
-  if (tr) {                                                       \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();   \
-    tacc[k] += t_ - tm;                                           \
-    tm = t_;                                                      \
-  }
-  for (size_t idx = tid; idx < t2_lds_doubles(N); idx += nt) smem[idx] = 0.0;
-  __syncthreads();
-  // symmetrise from the lower triangle (CMAES.cpp.base:908-913): upper
-  // element (r, c > r) = C[c][r]; diagonal C[r][r]
-  for (int idx = tid; idx < N * N; idx += nt) {
-    const int r = idx / N, c = idx % N;
-    if (c > r) M[(size_t)r * lda + c] = C[(size_t)c * N + r];
-    else if (c == r) dg[r] = C[(size_t)r * N + r];
-  }
-  __syncthreads();
-  for (int i = 0; i + 2 < N; i++) {
-    const int n = N - i - 1, par = i & 1;
-    double *va = vA(par), *tva = tvA(par), *xa = xA(par);
-    // ---- A (wave 0): Householder vector of pivot row i; alpha = M[i][i+1],
-    // dnrm2 over x_e = M[i][i+2+e], e < n-1
-    if (wid == 0) {
-      const double *prow = M + (size_t)i * lda;
-      const int m = n - 1;
-      const double alpha = prow[i + 1];
-      const double x0 = prow[i + 2 + min(lane, m - 1)], x1 = prow[i + 2 + min(lane + 64, m - 1)];
-      const double xnorm = dnrm2_regs(x0, x1, m, sv, tr, tacc + 8, tm);
-      T2_MARK(6)
-      double tau_i = 0.0, f1 = 1.0, f2 = 1.0, beta = 0.0;
-      int branch = 0;
-      if (xnorm != 0) {
-        beta = -(alpha >= 0.0 ? 1.0 : -1.0) * hypot_fast(alpha, xnorm);
-        const double sgap = alpha - beta;
-        const bool big = fabs(sgap) > DMIN;
-        tau_i = (beta - alpha) / beta;
-        f1 = (big ? 1.0 : EPS) / sgap;  // independent of tau: both divisions in flight
-        f2 = big ? 1.0 : 1.0 / EPS;
-        branch = big ? 1 : 2;
-      }
-      const double v0out = branch ? beta : alpha;
-      T2_MARK(7)
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int e = lane + 64 * h;
-        if (e < m) {
-          double t = h ? x1 : x0;
-          if (branch != 0) {
-            t = t * f1;
-            if (branch == 2) t = t * f2;
-          }
-          gH[(size_t)i * N + 1 + e] = t;
-          va[i + 2 + e] = t;
-          tva[i + 2 + e] = tau_i * t;
-        }
-      }
-      if (lane == 0) {
-        gH[(size_t)i * N] = v0out;
-        va[i + 1] = 1.0;
-        tva[i + 1] = tau_i * 1.0;
-        scal[0] = tau_i;
-        tauOut[i] = tau_i;
-        sdOut[i] = v0out;
-      }
-    }
-    T2_MARK(0)
-    __syncthreads();
-    T2_MARK(1)
-    const double tau_i = scal[0];
-    if (tau_i == 0.0) continue;  // no update this step (uniform)
-    // ---- E: dsymv chains, lockstep over columns; wave 0/1 descending for
-    // rows j < 64 / j >= 64, wave 2/3 ascending (row r = i+1+j)
-    if (wid < 4) {
-      const int h = wid & 1, j = lane + 64 * h;
-      const bool valid = j < n;
-      const int r = valid ? i + 1 + j : N - 1;  // invalid lanes walk a zero row / discard
-      if (wid < 2) {
-        // c = N-1 down to r+1, then the diagonal term: T = n-1-jmin steps
-        const double acc = lockstep_chain<-1>(tva + (N - 1), M + (size_t)r * lda + (N - 1), 1, max(0, n - 1 - 64 * h));
-        if (valid) xd[j] = acc + tva[r] * dg[r];
-      } else {
-        // c = i+1 up to r-1: T = largest j of the wave
-        const double acc =
-            lockstep_chain<1>(va + (i + 1), M + (size_t)(i + 1) * lda + r, lda, 64 * h < n ? min(n, 64 * h + 64) - 1 : 0);
-        if (valid) t2[j] = acc;
-      }
-    }
-    T2_MARK(2)
-    __syncthreads();
-    T2_MARK(3)
-    // ---- G, I, K (wave 0): x = xd + tau t2 and the xv products, the xv
-    // chain, alpha = -(tau/2) xv, x += alpha v
-    if (wid == 0) {
-      double xr[2];
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int j = lane + 64 * h;
-        xr[h] = 0.0;
-        if (j < n) {
-          xr[h] = xd[j] + tau_i * t2[j];
-          sv[j] = xr[h] * va[i + 1 + j];
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const double alpha = -(tau_i / 2.0) * lds_chain_add(0.0, sv, n);
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int j = lane + 64 * h;
-        if (j < n) xa[i + 1 + j] = xr[h] + alpha * va[i + 1 + j];
-      }
-    }
-    T2_MARK(4)
-    __syncthreads();
-    // ---- M: rank-2 update of the upper triangle and the diagonal; wave 0
-    // updates the next pivot row (i+1) and goes straight on to its dnrm2
-    const int r1 = i + 1;
-    if (wid == 0) {
-      const double nvr = -1.0 * va[r1], nxr = -1.0 * xa[r1];
-      double *row = M + (size_t)r1 * lda;
-      for (int c = r1 + 1 + lane; c < N; c += 64) row[c] += nvr * xa[c] + nxr * va[c];
-      if (lane == 0) dg[r1] += nvr * xa[r1] + nxr * va[r1];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-      // rows r = i+2+jr (jr < n-1) over waves 1..15; lane's columns c = r+1+lane, r+65+lane
-      for (int jr = wid - 1; jr < n - 1; jr += 15) {
-        const int r = r1 + 1 + jr;
-        const double nvr = -1.0 * va[r], nxr = -1.0 * xa[r];
-        double *row = M + (size_t)r * lda;
-        for (int c = r + 1 + lane; c < N; c += 64) row[c] += nvr * xa[c] + nxr * va[c];
-      }
-      // diagonal entries of rows i+2.. (threads 64 .. 64+n-2)
-      const int q = tid - 64;
-      if (q < n - 1) {
-        const int r = r1 + 1 + q;
-        const double nvr = -1.0 * va[r], nxr = -1.0 * xa[r];
-        dg[r] += nvr * xa[r] + nxr * va[r];
-      }
-    }
-    T2_MARK(5)
-  }
-  __syncthreads();
-#undef T2_MARK
-  if (tr) {
-    for (int k = 0; k < 6; k++) trace[8 + k] += tacc[k];
-    trace[29] += tacc[6];
-    trace[30] += tacc[7];
-    trace[31] += tacc[8];
-  }
-  for (int r = tid; r < N; r += nt) {
-    dOut[r] = dg[r];
-    if (r == N - 2) sdOut[r] = M[(size_t)r * lda + r + 1];
-  }
-}
-
 // Phase B for N > 128: the columns of Q are independent under
 // householder_hm, so workgroups own UMW_COLS columns each (Q^T rows in LDS)
 // and apply all reflectors without talking to each other; the next
@@ -2125,17 +966,13 @@ size_t umw_lds_bytes(int N) { return (2 * (size_t)UMW_COLS * (N + 1) + 3 * (size
 // (KORALI_AMD_UNPACK_ALLH=0 forces the streamed rows)
 __host__ __device__ inline size_t umw_hoff(int N, int i) { return (size_t)i * (N - 1) - (size_t)i * (i - 1) / 2; }
 __host__ __device__ inline size_t umw_hall_doubles(int N) { return N >= 3 ? umw_hoff(N, N - 2) : 0; }
-bool umw_all_fits(int N) {
-  if (const char *e = getenv("KORALI_AMD_UNPACK_ALLH"))
-    if (!atoi(e)) return false;
-  return N >= 3 && umw_lds_bytes(N) + umw_hall_doubles(N) * sizeof(double) <= 150 * 1024;
-}
+bool umw_all_fits(int N) { return N >= 3 && umw_lds_bytes(N) + umw_hall_doubles(N) * sizeof(double) <= 150 * 1024; }
 
 template <bool kAllH>
 __global__ void __launch_bounds__(UMW_TPB) k_unpack_mw(int N, const double *__restrict__ gH,
                                                        const double *__restrict__ tau, double *gQt) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nt = blockDim.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
   const int P = gridDim.x, g = blockIdx.x, lda = N + 1;
   double *Q = smem;                              // local k = column g + k P of Q
   double *hb = Q + (size_t)UMW_COLS * lda;       // 2 x N
@@ -2232,11 +1069,8 @@ constexpr int UWV_WAVES = 4, UWV_SV = 128 + 48;  // columns per workgroup; per-w
 __host__ __device__ inline size_t uwv_lds_bytes(int N) {
   return (umw_hall_doubles(N) + (size_t)N + (size_t)UWV_WAVES * UWV_SV) * sizeof(double);
 }
-bool uwv_fits(int N) {
-  if (const char *e = getenv("KORALI_AMD_UNPACK"))
-    if (!strcmp(e, "mw")) return false;
-  return N >= 3 && N <= 128 && uwv_lds_bytes(N) <= 150 * 1024;
-}
+// (KORALI_AMD_UNPACK=mw forces k_unpack_mw where it fits)
+bool uwv_fits(int N) { return N >= 3 && N <= 128 && uwv_lds_bytes(N) <= 150 * 1024; }
 __global__ void __launch_bounds__(64 * UWV_WAVES) k_unpack_wv(int N, const double *__restrict__ gH,
                                                              const double *__restrict__ tau, double *gQt) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -2431,11 +1265,6 @@ constexpr int APPLY_TPB = 256;
 template <int TEAM> struct ApplyGeom {
   static constexpr int ROWS = APPLY_TPB / TEAM;
 };
-static int apply_team() {
-  static const int t = (getenv("KORALI_AMD_APPLY_TEAM") && atoi(getenv("KORALI_AMD_APPLY_TEAM")) == 16) ? 16 : 64;
-  return t;
-}
-static int apply_rows() { return APPLY_TPB / apply_team(); }
 constexpr int APF = 4;  // apply: rotations prefetched ahead of the systolic replay
 
 // x of lane l-1 within the team (16 lanes: row_shr:1 within each DPP row;
@@ -2940,7 +1769,7 @@ __global__ void __launch_bounds__(256) k_publish_dsd(int N, const double *__rest
   }
 }
 
-// tri == 6: the covariance's lower triangle into host-coherent memory (rows
+// Tridiag::Host: the covariance's lower triangle into host-coherent memory (rows
 // of stride ldh, 16-byte stores of column pairs (c, c+1), c even, c <= r;
 // one wave per row, rows dealt round-robin over the workgroups), then a
 // sequence flag the host tridiagonalisation busy-polls.  Every thread fences
@@ -2975,7 +1804,7 @@ __global__ void __launch_bounds__(64 * PUBC_WAVES) k_publish_c(int N, const doub
 }
 inline int pubc_groups(int N) { return std::max(1, std::min(64, (N + PUBC_WAVES - 1) / PUBC_WAVES)); }
 
-// tri == 6: waits for the host tridiagonalisation's flag, then copies the
+// Tridiag::Host: waits for the host tridiagonalisation's flag, then copies the
 // reflectors (row i: the N-1-i entries the unpack reads) and tau[0..N-2)
 // from host-coherent memory into the device workspace (system-scope loads:
 // no stale line of an earlier generation; 16 in flight per thread).
@@ -3029,15 +1858,79 @@ size_t tridiag_vec_bytes(int N) { return (size_t)(3 * N + 16 + (N > 64 ? N : 64)
 // ones measured faster (C2, N = 128: 0.89 + 0.21 ms vs 0.95 + 0.38 ms)
 bool eig_use_lds(int N) { return N < 96 && eig_mat_bytes(N) + tridiag_vec_bytes(N) + 256 <= 160 * 1024; }
 
+using Tridiag = EigenPlan::Tridiag;
+using Unpack = EigenPlan::Unpack;
+
+// The tridiagonalisation of a handle.  On the device: one workgroup with the
+// whole matrix in LDS while it fits (k_tridiag_sq; no in-launch hand-offs),
+// else the older one-workgroup kernel while the one-workgroup phases are in
+// use (oneWg), else multi-workgroup (k_tridiag_mw2 while its rows fit).
+// forced (KORALI_AMD_TRIDIAG = sq | mw2 | lds | mw) selects a device kind
+// where it fits N; without it, KORALI_AMD_EIGEN_MW_MIN (mwMin) at or below N
+// selects the multi-workgroup kernels.  The host core's tridiagonalisation
+// (kg_host_tridiag.cpp) wherever the chase runs there too, up to hostMax
+// (KORALI_AMD_HOST_TRIDIAG_MAX); KORALI_AMD_TRIDIAG = host | a device kind
+// forces one.  wantRows: KORALI_AMD_TMW_ROWS, 0 unset.
+Tridiag choose_tridiag(int N, bool hostChase, const char *forced, bool oneWg, bool mwMin, int hostMax, int wantRows) {
+  const bool mw2 = mw2_fits(N, mw2_rows(N, wantRows ? wantRows : (N + 255) / 256));
+  const Tridiag multi = mw2 ? Tridiag::Mw2 : Tridiag::Mw;
+  Tridiag t = sq_fits(N) ? Tridiag::Sq : (oneWg ? Tridiag::Lds : multi);
+  if (forced) {
+    if (!strcmp(forced, "sq") && sq_fits(N)) t = Tridiag::Sq;
+    if (!strcmp(forced, "mw2") && mw2) t = Tridiag::Mw2;
+    if (!strcmp(forced, "lds") && eig_use_lds(N)) t = Tridiag::Lds;
+    if (!strcmp(forced, "mw")) t = Tridiag::Mw;
+  } else if (mwMin && !oneWg) {
+    t = multi;
+  }
+  if (hostChase && N >= 3 && (forced ? !strcmp(forced, "host") : N <= hostMax)) t = Tridiag::Host;
+  return t;
+}
+
+// wave: k_unpack_wv allowed (KORALI_AMD_UNPACK=mw takes it away); allH:
+// k_unpack_mw may hold every reflector row in LDS (KORALI_AMD_UNPACK_ALLH=0: streamed)
+Unpack choose_unpack(int N, bool oneWg, bool wave, bool allH) {
+  if (oneWg) return Unpack::OneWg;
+  if (wave && uwv_fits(N)) return Unpack::Wave;
+  return allH && umw_all_fits(N) ? Unpack::MwAllH : Unpack::MwStream;
+}
+
 int EigenSolver::init(int N_, bool hostChase_) {
   N = N_;
   hostChase = hostChase_;
   maxRot = 8 * N * N + 65536;  // GSL's implicit QR needs ~1.1 N^2 rotations
+
+  // every switch is read here, once per handle
+  const char *forced = getenv("KORALI_AMD_TRIDIAG");
+  if (forced) {
+    bool known = false;
+    for (const char *k : {"host", "sq", "mw2", "lds", "mw"}) known = known || !strcmp(forced, k);
+    KG_CHECK(known, std::string("eigensolver: KORALI_AMD_TRIDIAG=\"") + forced +
+                        "\" is not one of host | sq | mw2 | lds | mw");
+  }
+  const char *mwMin = getenv("KORALI_AMD_EIGEN_MW_MIN");  // multi-workgroup phases from this N up
+  const bool oneWg = eig_use_lds(N) && !(mwMin && N >= atoi(mwMin));
+  int hostMax = 512, wantRows = 0;
+  if (const char *e = getenv("KORALI_AMD_HOST_TRIDIAG_MAX")) hostMax = atoi(e);
+  if (const char *e = getenv("KORALI_AMD_TMW_ROWS")) wantRows = std::max(1, atoi(e));
+  plan.tridiag = choose_tridiag(N, hostChase, forced, oneWg, mwMin != nullptr, hostMax, wantRows);
+  {
+    const char *u = getenv("KORALI_AMD_UNPACK"), *a = getenv("KORALI_AMD_UNPACK_ALLH");
+    plan.unpack = choose_unpack(N, oneWg, !(u && !strcmp(u, "mw")), !(a && !atoi(a)));
+  }
+  plan.sqDpp = true;  // measured round 4: 0.495 -> 0.450 ms per C2 tridiagonalisation (bench_sq0 / bench_sq1)
+  if (const char *e = getenv("KORALI_AMD_SQ_DPP")) plan.sqDpp = *e == '1';
+  {
+    const char *e = getenv("KORALI_AMD_APPLY_TEAM");
+    plan.applyTeam = (e && atoi(e) == 16) ? 16 : 64;
+    plan.applyRows = APPLY_TPB / plan.applyTeam;
+  }
+  if (const char *e = getenv("KORALI_AMD_CHASE_PUBLISH_EVERY")) plan.chaseEvery = std::max(1, atoi(e));
+  if (const char *e = getenv("KORALI_AMD_CHASE_FUSED")) plan.chaseFused = *e != '0';
+
   const size_t mat = (size_t)N * (N + 1);
-  KG_HIP(dev_alloc(&gA, mat * sizeof(double)));
   KG_HIP(dev_alloc(&gH, (size_t)N * N * sizeof(double)));
   KG_HIP(dev_alloc(&gQt, mat * sizeof(double)));
-  KG_HIP(dev_alloc(&gWork, mat * sizeof(double)));
   KG_HIP(dev_alloc(&tau, (size_t)N * sizeof(double)));
   KG_HIP(dev_alloc(&dsd, 2 * (size_t)N * sizeof(double)));
   KG_HIP(dev_alloc(&chaseWork, 4 * (size_t)N * sizeof(double)));
@@ -3075,92 +1968,82 @@ int EigenSolver::init(int N_, bool hostChase_) {
     KG_HIP(hipEventCreateWithFlags(&ev_dsd, hipEventDisableTiming));
     KG_HIP(hipEventCreateWithFlags(&ev_chase, hipEventDisableTiming));
   }
-  lds = eig_use_lds(N);
-  if (const char *e = getenv("KORALI_AMD_EIGEN_MW_MIN"))  // multi-workgroup phases from this N up
-    if (N >= atoi(e)) lds = false;
-  // tridiagonalisation: one workgroup with the whole matrix in LDS while it
-  // fits (no in-launch hand-offs), multi-workgroup above;
-  // KORALI_AMD_TRIDIAG = lds | 1wg | mw forces one
-  tri = sq_fits(N) ? 4 : (t2_fits(N) ? 3 : (t1_fits(N) ? 1 : (lds ? 0 : (mw2_fits(N) ? 5 : 2))));
-  if (const char *e = getenv("KORALI_AMD_TRIDIAG")) {
-    if (!strcmp(e, "sq") && sq_fits(N)) tri = 4;
-    if (!strcmp(e, "mw2") && mw2_fits(N)) tri = 5;
-    if (!strcmp(e, "lds") && eig_use_lds(N)) tri = 0;
-    if (!strcmp(e, "1wg") && t1_fits(N)) tri = 1;
-    if (!strcmp(e, "1wg2") && t2_fits(N)) tri = 3;
-    if (!strcmp(e, "mw")) tri = 2;
-  } else if (getenv("KORALI_AMD_EIGEN_MW_MIN") && !lds) {
-    tri = mw2_fits(N) ? 5 : 2;
-  }
-  // the host core's tridiagonalisation (kg_host_tridiag.cpp) wherever the
-  // chase runs there too, up to KORALI_AMD_HOST_TRIDIAG_MAX (default 512;
-  // KORALI_AMD_TRIDIAG=host | a device kind forces one)
-  {
-    int hmax = 512;
-    if (const char *e = getenv("KORALI_AMD_HOST_TRIDIAG_MAX")) hmax = atoi(e);
-    const char *e = getenv("KORALI_AMD_TRIDIAG");
-    if (hostChase && N >= 3 && ((e && !strcmp(e, "host")) || (!e && N <= hmax))) tri = 6;
-  }
-  if (tri == 6) {
-    const unsigned fl = hipHostMallocCoherent | hipHostMallocMapped;
-    ldc = (N + 1) & ~1;
-    KG_HIP(host_alloc(&h_C, (size_t)N * ldc * sizeof(double), fl));
-    KG_HIP(hipHostGetDevicePointer((void **)&d_C_map, h_C, 0));
-    KG_HIP(host_alloc(&h_H, ((size_t)N * N + N) * sizeof(double), fl));
-    KG_HIP(hipHostGetDevicePointer((void **)&d_H_map, h_H, 0));
-    KG_CHECK(htri.init(N) == 0, "eigensolver: host tridiagonalisation workspace");
-    KG_HIP(dev_alloc(&pubDone, 64));
-    if (zero_fill(pubDone, 64)) return 1;
-  }
-  if (const char *e = getenv("KORALI_AMD_T1_FLAGS")) t1flags = atoi(e);
-  sqDpp = true;  // measured round 4: 0.495 -> 0.450 ms per C2 tridiagonalisation (bench_sq0 / bench_sq1)
-  if (const char *e = getenv("KORALI_AMD_SQ_DPP")) sqDpp = *e == '1';
-  if (tri == 1)
-    KG_HIP(allow_dynamic_lds((const void *)k_tridiag_1wg, (int)(t1_lds_doubles(N) * sizeof(double))));
-  if (tri == 4)
-    KG_HIP(allow_dynamic_lds((const void *)k_tridiag_sq<false>, (int)(sq_lds_doubles(N) * sizeof(double))));
-  if (tri == 4)
-    KG_HIP(allow_dynamic_lds((const void *)k_tridiag_sq<true>, (int)(sq_lds_doubles(N) * sizeof(double))));
-  if (tri == 3)
-    KG_HIP(allow_dynamic_lds((const void *)k_tridiag_1wg2, (int)(t2_lds_doubles(N) * sizeof(double))));
-  if (tri == 5) {
-    // the workgroups hand data to each other inside the launch: they must be
-    // co-resident, which a cooperative launch guarantees (or refuses).  With
-    // fewer co-resident slots than workgroups (fewer CUs visible, another
-    // kernel's LDS), each workgroup takes more rows.
-    int perCU = 0, dev = 0, cus = 0;
-    KG_HIP(hipGetDevice(&dev));
-    KG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    for (int rw = (N + 255) / 256; rw <= N; rw++) {
-      g_mw2_rw[N] = rw;
-      if (!mw2_fits(N) || mw2_rows(N) != rw) break;  // LDS exhausted (or rows forced by the environment)
-      KG_HIP(allow_dynamic_lds((const void *)k_tridiag_mw2<false>, (int)mw2_lds_bytes(N)));
-      KG_HIP(allow_dynamic_lds((const void *)k_tridiag_mw2<true>, (int)mw2_lds_bytes(N)));
-      KG_HIP(resident_per_cu(sqDpp ? (const void *)k_tridiag_mw2<true> : (const void *)k_tridiag_mw2<false>, MW2_TPB,
-                             mw2_lds_bytes(N), &perCU, nullptr));
-      if (getenv("KORALI_AMD_DEBUG_OCC"))
-        fprintf(stderr, "[korali_amd] mw2 N=%d rows=%d groups=%d lds=%zu perCU=%d cus=%d\n", N, rw, mw2_groups(N),
-                mw2_lds_bytes(N), perCU, cus);
-      if (perCU * cus >= mw2_groups(N)) break;
+
+  // what the planned launches need: buffers and dynamic-LDS limits
+  switch (plan.tridiag) {
+    case Tridiag::Host: {
+      const unsigned fl = hipHostMallocCoherent | hipHostMallocMapped;
+      ldc = (N + 1) & ~1;
+      KG_HIP(host_alloc(&h_C, (size_t)N * ldc * sizeof(double), fl));
+      KG_HIP(hipHostGetDevicePointer((void **)&d_C_map, h_C, 0));
+      KG_HIP(host_alloc(&h_H, ((size_t)N * N + N) * sizeof(double), fl));
+      KG_HIP(hipHostGetDevicePointer((void **)&d_H_map, h_H, 0));
+      KG_CHECK(htri.init(N) == 0, "eigensolver: host tridiagonalisation workspace");
+      KG_HIP(dev_alloc(&pubDone, 64));
+      if (zero_fill(pubDone, 64)) return 1;
+      break;
     }
-    KG_CHECK(mw2_fits(N) && perCU * cus >= mw2_groups(N),
-             "eigensolver: the multi-workgroup tridiagonalisation's " + std::to_string(mw2_groups(N)) +
-                 " workgroups cannot be co-resident (" + std::to_string(cus) + " CUs x " + std::to_string(perCU) +
-                 " per CU)");
+    case Tridiag::Sq:
+      KG_HIP(allow_dynamic_lds((const void *)k_tridiag_sq<false>, (int)(sq_lds_doubles(N) * sizeof(double))));
+      KG_HIP(allow_dynamic_lds((const void *)k_tridiag_sq<true>, (int)(sq_lds_doubles(N) * sizeof(double))));
+      break;
+    case Tridiag::Lds:
+      KG_HIP(allow_dynamic_lds((const void *)k_tridiag, 160 * 1024));
+      break;
+    case Tridiag::Mw:
+      plan.mwRows = tmw_rows(N, wantRows);
+      plan.mwGroups = (N + plan.mwRows - 1) / plan.mwRows;
+      plan.mwLds = tmw_lds_bytes(N, plan.mwRows);
+      KG_HIP(allow_dynamic_lds((const void *)k_tridiag_mw, (int)plan.mwLds));
+      break;
+    case Tridiag::Mw2: {
+      // the workgroups hand data to each other inside the launch: they must be
+      // co-resident, which a cooperative launch guarantees (or refuses).  With
+      // fewer co-resident slots than workgroups (fewer CUs visible, another
+      // kernel's LDS), each workgroup takes more rows.
+      int perCU = 0, dev = 0, cus = 0, rows = 0, groups = 0;
+      KG_HIP(hipGetDevice(&dev));
+      KG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+      for (int rw = (N + 255) / 256; rw <= N; rw++) {
+        rows = mw2_rows(N, wantRows ? wantRows : rw);
+        groups = (N + rows - 1) / rows;
+        if (!mw2_fits(N, rows) || rows != rw) break;  // LDS exhausted (or rows forced by the environment)
+        KG_HIP(allow_dynamic_lds((const void *)k_tridiag_mw2<false>, (int)mw2_lds_bytes(N, rows)));
+        KG_HIP(allow_dynamic_lds((const void *)k_tridiag_mw2<true>, (int)mw2_lds_bytes(N, rows)));
+        KG_HIP(resident_per_cu(plan.sqDpp ? (const void *)k_tridiag_mw2<true> : (const void *)k_tridiag_mw2<false>,
+                               MW2_TPB, mw2_lds_bytes(N, rows), &perCU, nullptr));
+        if (getenv("KORALI_AMD_DEBUG_OCC"))
+          fprintf(stderr, "[korali_amd] mw2 N=%d rows=%d groups=%d lds=%zu perCU=%d cus=%d\n", N, rows, groups,
+                  mw2_lds_bytes(N, rows), perCU, cus);
+        if (perCU * cus >= groups) break;
+      }
+      KG_CHECK(mw2_fits(N, rows) && perCU * cus >= groups,
+               "eigensolver: the multi-workgroup tridiagonalisation's " + std::to_string(groups) +
+                   " workgroups cannot be co-resident (" + std::to_string(cus) + " CUs x " + std::to_string(perCU) +
+                   " per CU)");
+      plan.mwRows = rows;
+      plan.mwGroups = groups;
+      plan.mwLds = mw2_lds_bytes(N, rows);
+      break;
+    }
   }
-  if (!lds || tri == 2 || tri == 5) {
+  if (plan.tridiag == Tridiag::Mw || plan.tridiag == Tridiag::Mw2)
     KG_HIP(dev_alloc(&comm, tmw_comm_words(N) * sizeof(unsigned long long)));
-    KG_HIP(allow_dynamic_lds((const void *)k_tridiag_mw, (int)tmw_lds_bytes(N)));
-    if (uwv_fits(N))
+  switch (plan.unpack) {
+    case Unpack::OneWg:
+      KG_HIP(allow_dynamic_lds((const void *)k_unpack, 160 * 1024));
+      break;
+    case Unpack::Wave:
       KG_HIP(allow_dynamic_lds((const void *)k_unpack_wv, (int)uwv_lds_bytes(N)));
-    if (umw_all_fits(N))
-      KG_HIP(allow_dynamic_lds((const void *)k_unpack_mw<true>, (int)(umw_lds_bytes(N) + umw_hall_doubles(N) * sizeof(double))));
-    else
+      break;
+    case Unpack::MwAllH:
+      KG_HIP(allow_dynamic_lds((const void *)k_unpack_mw<true>,
+                               (int)(umw_lds_bytes(N) + umw_hall_doubles(N) * sizeof(double))));
+      break;
+    case Unpack::MwStream:
       KG_HIP(allow_dynamic_lds((const void *)k_unpack_mw<false>, (int)umw_lds_bytes(N)));
+      break;
   }
-  const int attr = 160 * 1024;
-  KG_HIP(allow_dynamic_lds((const void *)k_tridiag<true>, attr));
-  KG_HIP(allow_dynamic_lds((const void *)k_unpack<true>, attr));
   KG_HIP(allow_dynamic_lds((const void *)k_apply<false, 64>, (int)apply_lds_bytes(N, 4)));
   KG_HIP(allow_dynamic_lds((const void *)k_apply<true, 64>, (int)apply_lds_bytes(N, 4)));
   KG_HIP(allow_dynamic_lds((const void *)k_apply<false, 16>, (int)apply_lds_bytes(N, 16)));
@@ -3174,8 +2057,8 @@ void EigenSolver::drain() {
 
 EigenSolver::~EigenSolver() {
   drain();
-  for (void *p : {(void *)gA, (void *)gH, (void *)gQt, (void *)gWork, (void *)tau, (void *)dsd, (void *)chaseWork,
-                  (void *)dev.hdr, (void *)dev.cs, (void *)dev.meta, (void *)dev.eval, (void *)dev.perm, (void *)comm,
+  for (void *p : {(void *)gH, (void *)gQt, (void *)tau, (void *)dsd, (void *)chaseWork, (void *)dev.hdr,
+                  (void *)dev.cs, (void *)dev.meta, (void *)dev.eval, (void *)dev.perm, (void *)comm,
                   (void *)dprogDev, (void *)pubDone})
     if (p) dev_release(p);
   for (void *p : {(void *)h_dsd, (void *)host.hdr, (void *)host.cs, (void *)host.meta, (void *)host.eval,
@@ -3195,7 +2078,7 @@ int EigenSolver::run_begin(const double *C, int diagonal, double *B, double *D, 
   if (begun) return 0;  // (already issued for this C: kg_cmaes_update publishes it ahead of k_sigma)
   begun = true;
   if (diagonal) return 0;  // k_eigen_diag runs in run_finish
-  if (tri == 6) {  // C to the host core; the rest waits for it in run_finish
+  if (plan.tridiag == Tridiag::Host) {  // C to the host core; the rest waits for it in run_finish
     cSeq = ++pubSeq;  // (a new value per publication: a re-published C is never mistaken for the last one)
     if (prof) prof(profCtx, "eigen_publish_c", 0);
     hipLaunchKernelGGL(k_publish_c, dim3(pubc_groups(N)), dim3(64 * PUBC_WAVES), 0, s, N, C, d_C_map, ldc, dprog + 2,
@@ -3204,46 +2087,39 @@ int EigenSolver::run_begin(const double *C, int diagonal, double *B, double *D, 
     if (prof) prof(profCtx, "eigen_publish_c", 1);
     return 0;
   }
-  const size_t matb = lds ? eig_mat_bytes(N) : 0;
   double *d = dsd, *sd = dsd + N;
   if (prof) prof(profCtx, "eigen_tridiag", 0);
-  const bool fusedPublish = hostChase && tri == 4;  // the one-workgroup kernel publishes d | sd itself
+  // the one-workgroup kernel publishes d | sd itself
+  const bool fusedPublish = hostChase && plan.tridiag == Tridiag::Sq;
   if (fusedPublish) dsdSeq = ++pubSeq;  // (unique per publication, as cSeq)
-  if (tri == 4) {
-    hipLaunchKernelGGL(sqDpp ? k_tridiag_sq<true> : k_tridiag_sq<false>, dim3(1), dim3(SQ_TPB),
-                       sq_lds_doubles(N) * sizeof(double), s, N, C, gH, tau, d, sd, trace,
-                       fusedPublish ? d_dsd_map : (double *)nullptr,
-                       fusedPublish ? dprog + 1 : (unsigned long long *)nullptr, (unsigned long long)dsdSeq);
-  }
-  else if (tri == 3)
-    hipLaunchKernelGGL(k_tridiag_1wg2, dim3(1), dim3(T2_TPB), t2_lds_doubles(N) * sizeof(double), s, N, C, gH, tau,
-                       d, sd, trace);
-  else if (tri == 1)
-    hipLaunchKernelGGL(k_tridiag_1wg, dim3(1), dim3(T1_TPB), t1_lds_doubles(N) * sizeof(double), s, N, C, gH, tau, d,
-                       sd, trace, t1flags);
-  else if (tri == 0)
-    hipLaunchKernelGGL(k_tridiag<true>, dim3(1), dim3(1024), eig_mat_bytes(N) + tridiag_vec_bytes(N), s, N, C, gA, gH,
-                       tau, d, sd, trace);
-  else if (tri == 5) {
-    KG_HIP(hipMemsetAsync(comm, 0, tmw_comm_words(N) * sizeof(unsigned long long), s));
-    int N_ = N;
-    const double *C_ = C;
-    double *gH_ = gH, *tau_ = tau, *d_ = d, *sd_ = sd;
-    unsigned long long *comm_ = comm, *trace_ = trace;
-    unsigned int *errors_ = errors;
-    void *args[] = {&N_, &C_, &gH_, &tau_, &d_, &sd_, &comm_, &errors_, &trace_};
-    KG_HIP(launch_resident(sqDpp ? (const void *)k_tridiag_mw2<true> : (const void *)k_tridiag_mw2<false>,
-                           dim3(mw2_groups(N)), dim3(MW2_TPB), args, mw2_lds_bytes(N),
-                           s));
-  } else {
-    KG_HIP(hipMemsetAsync(comm, 0, tmw_comm_words(N) * sizeof(unsigned long long), s));
-    int N_ = N;
-    const double *C_ = C;
-    double *gH_ = gH, *tau_ = tau, *d_ = d, *sd_ = sd;
-    unsigned long long *comm_ = comm, *trace_ = trace;
-    unsigned int *errors_ = errors;
-    void *args[] = {&N_, &C_, &gH_, &tau_, &d_, &sd_, &comm_, &errors_, &trace_};
-    KG_HIP(launch_resident((const void *)k_tridiag_mw, dim3(tmw_groups(N)), dim3(TMW_TPB), args, tmw_lds_bytes(N), s));
+  switch (plan.tridiag) {
+    case Tridiag::Sq:
+      hipLaunchKernelGGL(plan.sqDpp ? k_tridiag_sq<true> : k_tridiag_sq<false>, dim3(1), dim3(SQ_TPB),
+                         sq_lds_doubles(N) * sizeof(double), s, N, C, gH, tau, d, sd, trace,
+                         fusedPublish ? d_dsd_map : (double *)nullptr,
+                         fusedPublish ? dprog + 1 : (unsigned long long *)nullptr, (unsigned long long)dsdSeq);
+      break;
+    case Tridiag::Lds:
+      hipLaunchKernelGGL(k_tridiag, dim3(1), dim3(1024), eig_mat_bytes(N) + tridiag_vec_bytes(N), s, N, C, gH, tau, d,
+                         sd, trace);
+      break;
+    case Tridiag::Mw:
+    case Tridiag::Mw2: {
+      const bool mw2 = plan.tridiag == Tridiag::Mw2;
+      KG_HIP(hipMemsetAsync(comm, 0, tmw_comm_words(N) * sizeof(unsigned long long), s));
+      int N_ = N;
+      const double *C_ = C;
+      double *gH_ = gH, *tau_ = tau, *d_ = d, *sd_ = sd;
+      unsigned long long *comm_ = comm, *trace_ = trace;
+      unsigned int *errors_ = errors;
+      void *args[] = {&N_, &C_, &gH_, &tau_, &d_, &sd_, &comm_, &errors_, &trace_};
+      const void *f = !mw2 ? (const void *)k_tridiag_mw
+                           : (plan.sqDpp ? (const void *)k_tridiag_mw2<true> : (const void *)k_tridiag_mw2<false>);
+      KG_HIP(launch_resident(f, dim3(plan.mwGroups), dim3(mw2 ? MW2_TPB : TMW_TPB), args, plan.mwLds, s));
+      break;
+    }
+    case Tridiag::Host:
+      break;  // (returned above)
   }
   KG_HIP(hipGetLastError());
   if (prof) prof(profCtx, "eigen_tridiag", 1);
@@ -3267,21 +2143,53 @@ int EigenSolver::run_begin(const double *C, int diagonal, double *B, double *D, 
 
 // Phase B: Q from the reflectors in gH / tau (symmtd_unpack)
 int EigenSolver::launch_unpack(hipStream_t s, ProfileFn prof, void *profCtx) {
-  const size_t matb = lds ? eig_mat_bytes(N) : 0;
   if (prof) prof(profCtx, "eigen_unpack", 0);
-  if (lds)
-    hipLaunchKernelGGL(k_unpack<true>, dim3(1), dim3(1024), matb + 2 * N * sizeof(double), s, N, gH, tau, gQt);
-  else if (uwv_fits(N))
-    hipLaunchKernelGGL(k_unpack_wv, dim3((N + UWV_WAVES - 1) / UWV_WAVES), dim3(64 * UWV_WAVES), uwv_lds_bytes(N), s,
-                       N, gH, tau, gQt);
-  else if (umw_all_fits(N))
-    hipLaunchKernelGGL(k_unpack_mw<true>, dim3(umw_groups(N)), dim3(UMW_TPB),
-                       umw_lds_bytes(N) + umw_hall_doubles(N) * sizeof(double), s, N, gH, tau, gQt);
-  else
-    hipLaunchKernelGGL(k_unpack_mw<false>, dim3(umw_groups(N)), dim3(UMW_TPB), umw_lds_bytes(N), s, N, gH, tau,
-                       gQt);
+  switch (plan.unpack) {
+    case Unpack::OneWg:
+      hipLaunchKernelGGL(k_unpack, dim3(1), dim3(1024), eig_mat_bytes(N) + 2 * N * sizeof(double), s, N, gH, tau, gQt);
+      break;
+    case Unpack::Wave:
+      hipLaunchKernelGGL(k_unpack_wv, dim3((N + UWV_WAVES - 1) / UWV_WAVES), dim3(64 * UWV_WAVES), uwv_lds_bytes(N),
+                         s, N, gH, tau, gQt);
+      break;
+    case Unpack::MwAllH:
+      hipLaunchKernelGGL(k_unpack_mw<true>, dim3(umw_groups(N)), dim3(UMW_TPB),
+                         umw_lds_bytes(N) + umw_hall_doubles(N) * sizeof(double), s, N, gH, tau, gQt);
+      break;
+    case Unpack::MwStream:
+      hipLaunchKernelGGL(k_unpack_mw<false>, dim3(umw_groups(N)), dim3(UMW_TPB), umw_lds_bytes(N), s, N, gH, tau,
+                         gQt);
+      break;
+  }
   KG_HIP(hipGetLastError());
   if (prof) prof(profCtx, "eigen_unpack", 1);
+  return 0;
+}
+
+// Phase D: the rotations' replay on Q^T, one workgroup per 4 rows (16 with
+// 16-lane teams).  streamed: behind the host chase, which publishes chase
+// `seq` while the kernel runs; workgroup 0 is the fetcher, and the row
+// workgroups spin only on its progress word.  The fetcher is dispatched
+// first, so a plain launch on this stream is safe (launch_resident still
+// checks the grid fits the device).  Otherwise the device chase's record is
+// complete when the kernel starts.
+int EigenSolver::launch_apply(bool streamed, unsigned long long seq, double *B, double *D, double *minEig,
+                              double *maxEig, double *eigenFailures, unsigned int *errors, hipStream_t s) {
+  int N_ = N;
+  const double *gQt_ = gQt;
+  EigRec devRec = dev, mr = streamed ? (EigRec)hmap : devRec;
+  unsigned long long *trace_ = trace, *dprogDev_ = streamed ? dprogDev : nullptr, *dprog_ = streamed ? dprog : nullptr;
+  void *args[] = {&N_, &gQt_, &devRec, &B, &D, &minEig, &maxEig, &eigenFailures, &errors, &trace_,
+                  &dprogDev_, &seq, &mr, &dprog_};
+  const bool wave = plan.applyTeam == 64;
+  const void *f = streamed ? (wave ? (const void *)k_apply<true, 64> : (const void *)k_apply<true, 16>)
+                           : (wave ? (const void *)k_apply<false, 64> : (const void *)k_apply<false, 16>);
+  const int rows = plan.applyRows, groups = (N + rows - 1) / rows;
+  const size_t ldsBytes = apply_lds_bytes(N, rows);
+  if (streamed)
+    KG_HIP(launch_resident(f, dim3(groups + 1), dim3(APPLY_TPB), args, ldsBytes, s, /*prefer_plain=*/true));
+  else
+    KG_HIP(hipLaunchKernel(f, dim3(groups), dim3(APPLY_TPB), args, ldsBytes, s));
   return 0;
 }
 
@@ -3296,12 +2204,12 @@ int EigenSolver::run_finish(const double *C, int diagonal, double *B, double *D,
     KG_HIP(hipGetLastError());
     return 0;
   }
-  EigRec devRec = dev;
   if (hostChase) {
     // the apply kernel is queued behind the unpack and consumes the Givens
     // rotations as this core's serial chase publishes them
     const unsigned long long seq = ++chaseSeq;
-    if (tri == 6) {
+    const bool hostTri = plan.tridiag == Tridiag::Host;
+    if (hostTri) {
       // the reflectors' copy and the unpack are queued now and start the
       // moment the host core publishes them
       if (prof) prof(profCtx, "eigen_fetch_h", 0);
@@ -3312,26 +2220,8 @@ int EigenSolver::run_finish(const double *C, int diagonal, double *B, double *D,
       if (launch_unpack(s, prof, profCtx)) return 1;
     }
     if (prof) prof(profCtx, "eigen_apply", 0);
-    EigRec mr = hmap;
-    // the fetcher workgroup (0) + one workgroup per 4 rows (16 with 16-lane
-    // teams); the row workgroups spin only on the fetcher's progress word,
-    // and the fetcher is dispatched first, so a plain launch on this stream
-    // is safe (launch_resident still checks the grid fits the device)
-    {
-      int N_ = N;
-      const double *gQt_ = gQt;
-      double *B_ = B, *D_ = D, *minEig_ = minEig, *maxEig_ = maxEig, *eigenFailures_ = eigenFailures;
-      unsigned int *errors_ = errors;
-      unsigned long long *trace_ = trace, *dprogDev_ = dprogDev, *dprog_ = dprog;
-      unsigned long long seq_ = seq;
-      void *args[] = {&N_, &gQt_, &devRec, &B_, &D_, &minEig_, &maxEig_, &eigenFailures_, &errors_, &trace_,
-                      &dprogDev_, &seq_, &mr, &dprog_};
-      const int rows = apply_rows();
-      KG_HIP(launch_resident(rows == 4 ? (const void *)k_apply<true, 64> : (const void *)k_apply<true, 16>,
-                             dim3((N + rows - 1) / rows + 1), dim3(APPLY_TPB), args, apply_lds_bytes(N, rows), s,
-                             /*prefer_plain=*/true));
-    }
-    if (tri == 6) {
+    if (launch_apply(true, seq, B, D, minEig, maxEig, eigenFailures, errors, s)) return 1;
+    if (hostTri) {
       if (prof) prof(profCtx, "eigen_c_wait", 2);
       htri.wake();  // (the helper threads of a multi-threaded pass spin from here on)
       const auto t0 = std::chrono::steady_clock::now();
@@ -3368,32 +2258,14 @@ int EigenSolver::run_finish(const double *C, int diagonal, double *B, double *D,
     if (prof) prof(profCtx, "eigen_chase_host", 2);
     EigRec hr = host;
     chase_publish(hprog, chase_word(seq, 0, 0));
-    // the progress word every `every` QR steps (KORALI_AMD_CHASE_PUBLISH_EVERY;
-    // each write after a device poll of its line costs the core a miss)
-    static const int every = [] {
-      const char *e = getenv("KORALI_AMD_CHASE_PUBLISH_EVERY");
-      const int v = e ? atoi(e) : 1;
-      return v < 1 ? 1 : v;
-    }();
-    static const bool fused = [] {  // KORALI_AMD_CHASE_FUSED=0: the separate chop pass and rotation copy
-      const char *e = getenv("KORALI_AMD_CHASE_FUSED");
-      return !(e && *e == '0');
-    }();
-    qr_chase(N, h_dsd, h_dsd + N, hr, maxRot, hgc.data(), hgs.data(), hprog, seq, every, fused);
+    // the progress word every chaseEvery QR steps (each write after a device
+    // poll of its line costs the core a miss)
+    qr_chase(N, h_dsd, h_dsd + N, hr, maxRot, hgc.data(), hgs.data(), hprog, seq, plan.chaseEvery, plan.chaseFused);
     if (prof) prof(profCtx, "eigen_chase_host", 3);
   } else {
     KG_HIP(hipStreamWaitEvent(s, ev_chase, 0));
     if (prof) prof(profCtx, "eigen_apply", 0);
-    const int rows = apply_rows();
-    if (rows == 4)
-      hipLaunchKernelGGL((k_apply<false, 64>), dim3((N + rows - 1) / rows), dim3(APPLY_TPB), apply_lds_bytes(N, rows),
-                         s, N, gQt, devRec, B, D, minEig, maxEig, eigenFailures, errors, trace,
-                         (unsigned long long *)nullptr, 0ULL, devRec, (unsigned long long *)nullptr);
-    else
-      hipLaunchKernelGGL((k_apply<false, 16>), dim3((N + rows - 1) / rows), dim3(APPLY_TPB), apply_lds_bytes(N, rows),
-                         s, N, gQt, devRec, B, D, minEig, maxEig, eigenFailures, errors, trace,
-                         (unsigned long long *)nullptr, 0ULL, devRec, (unsigned long long *)nullptr);
-    KG_HIP(hipGetLastError());
+    if (launch_apply(false, 0, B, D, minEig, maxEig, eigenFailures, errors, s)) return 1;
   }
   if (prof) prof(profCtx, "eigen_apply", 1);
   return 0;

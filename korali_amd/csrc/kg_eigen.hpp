@@ -15,6 +15,26 @@ struct EigRec;
 // stream), 2/3 = begin/end of a host stage (wall clock)
 typedef void (*ProfileFn)(void *ctx, const char *stage, int phase);
 
+// Which kernels a handle launches and with what geometry: decided once, by
+// EigenSolver::init (from N, the chase's place and the KORALI_AMD_* switches
+// as they stand at creation), and only read afterwards.
+struct EigenPlan {
+  // phase A: k_tridiag (one workgroup, the older LDS kernel), k_tridiag_mw,
+  // k_tridiag_sq, k_tridiag_mw2, the host core (kg_host_tridiag.cpp)
+  enum class Tridiag { Lds, Mw, Sq, Mw2, Host };
+  // phase B: k_unpack (one workgroup), k_unpack_wv (one wave per column),
+  // k_unpack_mw with every reflector row in LDS / with the rows streamed
+  enum class Unpack { OneWg, Wave, MwAllH, MwStream };
+  Tridiag tridiag = Tridiag::Lds;
+  Unpack unpack = Unpack::OneWg;
+  bool sqDpp = true;  // k_tridiag_sq / _mw2: scalar chains on registers / DPP broadcasts (KORALI_AMD_SQ_DPP=0: LDS-streamed)
+  int mwRows = 0, mwGroups = 0;  // Mw / Mw2: rows per workgroup, workgroups
+  size_t mwLds = 0;              //           dynamic LDS bytes
+  int applyTeam = 64, applyRows = 4;  // k_apply: lanes per row team (KORALI_AMD_APPLY_TEAM=16), rows per workgroup
+  int chaseEvery = 1;      // host chase: progress word every so many QR steps (KORALI_AMD_CHASE_PUBLISH_EVERY)
+  bool chaseFused = true;  // KORALI_AMD_CHASE_FUSED=0: the separate chop pass and rotation copy
+};
+
 class EigenSolver {
  public:
   ~EigenSolver();
@@ -33,11 +53,9 @@ class EigenSolver {
   // the caller changed C after run_begin: the next run() starts over
   // (phase A again; a host hand-off is published again under a new sequence)
   void invalidate() { begun = false; }
-  // C reaches the host core for the tridiagonalisation (tri == 6): run_begin
-  // only publishes C, so a caller may issue it as soon as C is final
-  bool host_tridiag() const { return tri == 6; }
-  int t1flags = 0;  // KORALI_AMD_T1_FLAGS: experiment switches of k_tridiag_1wg
-  bool sqDpp = true;  // k_tridiag_sq's scalar chains on registers / DPP broadcasts (KORALI_AMD_SQ_DPP=0: LDS-streamed)
+  // C reaches the host core for the tridiagonalisation: run_begin only
+  // publishes C, so a caller may issue it as soon as C is final
+  bool host_tridiag() const { return plan.tridiag == EigenPlan::Tridiag::Host; }
   unsigned long long *trace = nullptr;  // optional device counters (k_tridiag sub-phases)
   // QR steps / Givens rotations of the last host chase (diagnostics)
   void last_counts(int &steps, int &rotations) const {
@@ -45,16 +63,17 @@ class EigenSolver {
     rotations = (hostChase && host.meta) ? host.meta[1] : -1;
   }
   bool hostChase = true;
-  int tridiag_kind() const { return tri; }  // (diagnostics)
-  // host-core tridiagonalisation (tri == 6): wall time of the last one (ms)
+  EigenPlan::Tridiag tridiag_kind() const { return plan.tridiag; }  // (diagnostics)
+  // host-core tridiagonalisation: wall time of the last one (ms)
   double last_host_tridiag_ms = 0.0;
 
  private:
   int N = 0, maxRot = 0;
-  bool lds = true;
-  int tri = 0;  // tridiagonalisation kernel: 0 k_tridiag (LDS), 1 k_tridiag_1wg, 2 k_tridiag_mw, 3 k_tridiag_1wg2, 4 k_tridiag_sq, 5 k_tridiag_mw2, 6 host core
+  EigenPlan plan;  // filled by init, constant afterwards
   int launch_unpack(hipStream_t s, ProfileFn prof, void *profCtx);
-  // tri == 6: C's lower triangle reaches the host through host-coherent
+  int launch_apply(bool streamed, unsigned long long seq, double *B, double *D, double *minEig, double *maxEig,
+                   double *eigenFailures, unsigned int *errors, hipStream_t s);
+  // Tridiag::Host: C's lower triangle reaches the host through host-coherent
   // memory (k_publish_c), the host writes the reflectors + tau back
   // (k_fetch_h copies them to gH / tau ahead of the unpack)
   HostTridiag htri;
@@ -62,8 +81,7 @@ class EigenSolver {
   int ldc = 0;  // row stride of h_C (even: 16-byte rows)
   unsigned int *pubDone = nullptr;  // k_publish_c's workgroup counter (device memory)
   unsigned long long cSeq = 0, pubSeq = 0;  // sequence of the C hand-off the host waits for; publications so far
-  double *gA = nullptr, *gH = nullptr, *gQt = nullptr, *gWork = nullptr, *tau = nullptr, *dsd = nullptr,
-         *chaseWork = nullptr;
+  double *gH = nullptr, *gQt = nullptr, *tau = nullptr, *dsd = nullptr, *chaseWork = nullptr;
   unsigned long long *comm = nullptr;  // in-launch hand-off granules (N > 128 tridiagonalisation)
   struct Rec {
     int *hdr = nullptr;

@@ -417,19 +417,15 @@ __host__ __device__ inline size_t mw2_lds_doubles(int N, int RW) {
   // M | Pd | Pa | prow (+16) | nrow | vloc | tv | xl | sv (+64) | scal, accb, t2b, mskb, cmx (16 each) | sa (+64)
   return (size_t)RW * (N + 1) + 2 * (size_t)RW * mw2_ps(N) + (N + 16) + 4 * (size_t)N + (N + 64) + 5 * 16 + (N + 64);
 }
-// rows per workgroup chosen at init for the device's co-resident capacity, by N
-// (0: the default); every handle of one N on this device arrives at the same value
-static int g_mw2_rw[1025];
-int mw2_rows(int N) {
-  int rw = (N <= 1024 && g_mw2_rw[N] > 0) ? g_mw2_rw[N] : (N + 255) / 256;
-  if (const char *e = getenv("KORALI_AMD_TMW_ROWS")) rw = atoi(e);
-  if (rw < 1) rw = 1;
+// rows per workgroup: `want` (the handle's search for the device's co-resident
+// capacity at init, or KORALI_AMD_TMW_ROWS), lowered until they fit in LDS
+int mw2_rows(int N, int want) {
+  int rw = want < 1 ? 1 : want;
   while (rw > 1 && mw2_lds_doubles(N, rw) * sizeof(double) > 150 * 1024) rw--;
   return rw;
 }
-int mw2_groups(int N) { return (N + mw2_rows(N) - 1) / mw2_rows(N); }
-size_t mw2_lds_bytes(int N) { return mw2_lds_doubles(N, mw2_rows(N)) * sizeof(double); }
-bool mw2_fits(int N) { return N > 16 && N <= 1024 && mw2_lds_doubles(N, mw2_rows(N)) * sizeof(double) <= 150 * 1024; }
+size_t mw2_lds_bytes(int N, int rows) { return mw2_lds_doubles(N, rows) * sizeof(double); }
+bool mw2_fits(int N, int rows) { return N > 16 && N <= 1024 && mw2_lds_bytes(N, rows) <= 150 * 1024; }
 
 // kDpp: the ssq and xv chains on register-held elements (kc_nrm2_dpp /
 // kc_add_dpp, 128 elements per call), as k_tridiag_sq<true>

@@ -8,11 +8,13 @@ eigen_cases.py (graded, clustered, block diagonal, zero columns, 1e-280 and
 dev["Covariance Matrix"] = M; dev.sample(), against the CPU oracle with the
 same assignment and prepare().  Every comparison is equality of bits.
 
-The configurations select the kernels: the six tridiagonalisations, the unpack
-forms, the host and the device chase, the streamed and the plain rotation
-replay; switches that the library reads once per process run in a child
-process (this file, started as a script).  test_eigen_cases_cpu.py pins the
-families and the oracle's handling of them on the CPU.
+The configurations select the kernels: the five tridiagonalisations (four on
+the device, one on the host core), the unpack forms, the host and the device
+chase, the streamed and the plain rotation replay.  Every switch is read when
+a handle is created; the team, chop-pass and progress-word switches also run
+in a child process (this file, started as a script), as when they were
+process-wide.  test_eigen_cases_cpu.py pins the families and the oracle's
+handling of them on the CPU.
 """
 import os
 import subprocess
@@ -113,7 +115,7 @@ def walk(N, chase="host", device_tridiag=None):
 # every switch that selects an eigensolver kernel: a test sets exactly its own
 SWITCHES = ("KORALI_AMD_TRIDIAG", "KORALI_AMD_SQ_DPP", "KORALI_AMD_EIGEN_MW_MIN", "KORALI_AMD_UNPACK",
             "KORALI_AMD_UNPACK_ALLH", "KORALI_AMD_EIGEN_CHASE", "KORALI_AMD_HOST_TRIDIAG_MAX", "KORALI_AMD_TMW_ROWS",
-            "KORALI_AMD_T1_FLAGS", "KORALI_AMD_APPLY_TEAM", "KORALI_AMD_CHASE_FUSED", "KORALI_AMD_CHASE_PUBLISH_EVERY")
+            "KORALI_AMD_APPLY_TEAM", "KORALI_AMD_CHASE_FUSED", "KORALI_AMD_CHASE_PUBLISH_EVERY")
 
 
 def setenv(monkeypatch, env):
@@ -142,13 +144,6 @@ def test_default_below_three_takes_the_device_path(monkeypatch, N):
 @pytest.mark.parametrize("dpp", ["0", "1"])
 def test_tridiag_sq(monkeypatch, dpp, N):
     setenv(monkeypatch, {"KORALI_AMD_TRIDIAG": "sq", "KORALI_AMD_SQ_DPP": dpp})
-    walk(N, device_tridiag=True)
-
-
-@pytest.mark.parametrize("N", [3, 17, 65, 128])
-@pytest.mark.parametrize("kind", ["1wg2", "1wg"])
-def test_tridiag_one_workgroup(monkeypatch, kind, N):
-    setenv(monkeypatch, {"KORALI_AMD_TRIDIAG": kind})
     walk(N, device_tridiag=True)
 
 
@@ -203,7 +198,31 @@ def test_device_chase(monkeypatch, tridiag, N):
     walk(N, chase="device", device_tridiag=True)
 
 
+def test_unknown_tridiag_kind_is_an_error(monkeypatch):
+    """A value outside host | sq | mw2 | lds | mw (a removed kernel's name, a
+    typo) fails the handle's creation and is quoted in the message."""
+    from korali_amd.native import KoraliDeviceError
+    setenv(monkeypatch, {"KORALI_AMD_TRIDIAG": "1wg2"})
+    with pytest.raises(KoraliDeviceError, match="1wg2"):
+        pair(3)
+
+
 # ------------------------------------------------------ process-wide switches
+
+TEAM_ENVS = [
+    {"KORALI_AMD_APPLY_TEAM": "16", "KORALI_AMD_CHASE_FUSED": "0", "KORALI_AMD_CHASE_PUBLISH_EVERY": "3"},
+    {"KORALI_AMD_APPLY_TEAM": "16"},
+]
+
+
+@pytest.mark.parametrize("N", [17, 65])
+@pytest.mark.parametrize("env", TEAM_ENVS, ids=["team16-unfused-every3", "team16"])
+def test_team_and_chase_switches_per_handle(monkeypatch, env, N):
+    """The same two environments in this process, after handles created
+    without them: the handle reads the switches at its creation."""
+    setenv(monkeypatch, env)
+    walk(N)
+
 
 CHILD_WALKS = ((3, "host"), (17, "host"), (65, "host"), (129, "host"), (17, "device"))
 

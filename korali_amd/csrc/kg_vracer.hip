@@ -2317,14 +2317,21 @@ VrGemmJob vr_gemm_job(int ep, int M, int N, int K, const float *A, long long sam
   return g;
 }
 
+// KORALI_AMD_VR_FUSED=1 selects k_vr_fwd_fused where its LDS holds the shapes:
+// hidden width up to 256, and a mini-batch's 16 gathered state rows within
+// the weight-chunk buffer they are staged in
+bool vr_fused(const Params &P) {
+  const char *fe = getenv("KORALI_AMD_VR_FUSED");
+  return P.H <= 256 && FR * P.S <= FK * FNP && fe && *fe == '1';
+}
+
 int vr_forward(kg_vracer_t h, const float *X, int M, float *out, bool input_done = false) {
   const Params &P = h->P;
   KG_CHECK((size_t)M <= h->rowsMax, "vracer: forward batch exceeds the allocated rows");
   // KORALI_AMD_VR_FUSED=1: one launch for the whole forward pass (bit-identical
   // results; measured slower than the per-layer kernels at C5, round 5: kept
   // for A/B and the equality test)
-  const char *fe = getenv("KORALI_AMD_VR_FUSED");
-  if (P.H <= 256 && fe && *fe == '1') {
+  if (vr_fused(P)) {
     VrStage tg(h, M == P.E ? "gemm_rollout" : (M == 2 * P.B ? "gemm_update" : "gemm_other"));
     hipLaunchKernelGGL(k_vr_fwd_fused<false>, dim3(vr_blocks(M, FR)), dim3(256), 0, h->stream, P, M, X,
                        (const float *)h->theta, (const long long *)h->offs, h->acts, (long long)h->rowsMax, out,
@@ -2399,19 +2406,25 @@ int vr_update(kg_vracer_t h, const unsigned *forced, const unsigned *drawn = nul
   const int B = P.B;
   KG_CHECK(h->st_host->size >= 2, "vracer: policy updates need at least two experiences in the replay memory");
   VrStage tu(h, "update");
-  const char *fe = getenv("KORALI_AMD_VR_FUSED");
-  const bool fused = P.H <= 256 && fe && *fe == '1';
+  const bool fused = vr_fused(P);
   if (fused) {
     // the mini-batch draw, its gather and the whole forward pass: one launch
     VrStage tg(h, "gemm_update");
     hipLaunchKernelGGL(k_vr_fwd_fused<true>, dim3(vr_blocks(2 * B, FR)), dim3(256), 0, h->stream, P, 2 * B,
                        (const float *)nullptr, (const float *)h->theta, (const long long *)h->offs, h->acts,
                        (long long)h->rowsMax, h->out, (const State *)h->st, h->er, h->mb, forced, h->Xmb);
-  } else if (drawn) {  // ids drawn ahead by the graph's k_vr_draw_ahead
+  } else if (drawn && P.S <= MAXS) {  // ids drawn ahead by the graph's k_vr_draw_ahead
     hipLaunchKernelGGL(k_vr_gather_in, dim3(vr_blocks(2LL * B * P.H, 256)), dim3(256), 0, h->stream, P,
                        (const State *)h->st, h->er, drawn, h->mb, h->Xmb, (const float *)(h->theta + h->offW[0]),
                        (const float *)(h->theta + h->offb[0]), h->acts);
     if (vr_forward(h, h->Xmb, 2 * B, h->out, true)) return 1;
+  } else if (drawn) {
+    // more state variables than k_vr_gather_in holds in registers (a host
+    // environment's state): the ids drawn ahead go through the one-workgroup
+    // gather as given ids (it leaves the draw counter alone; k_vr_meta
+    // advances it below), then k_vr_fwd_in
+    hipLaunchKernelGGL(k_vr_minibatch, dim3(1), dim3(1024), 0, h->stream, P, h->st, h->er, h->mb, drawn, h->Xmb);
+    if (vr_forward(h, h->Xmb, 2 * B, h->out)) return 1;
   } else if (vr_draw_in() && P.S <= 16) {
     hipLaunchKernelGGL(k_vr_minibatch_in, dim3(vr_blocks(2 * B, MI)), dim3(256), 0, h->stream, P, (const State *)h->st,
                        h->er, h->mb, forced, h->Xmb, (const float *)(h->theta + h->offW[0]),
@@ -2502,10 +2515,12 @@ struct VrField {
 bool vr_field(kg_vracer_t h, const char *name, VrField &f) {
   const Params &P = h->P;
   const size_t R = (size_t)P.R, E = (size_t)P.E;
+  const size_t B = (size_t)P.B, H = (size_t)P.H;
   struct {
     const char *n;
     void *p;
     size_t elem, count;
+    bool param;
   } tab[] = {
       {"state", h->er.st, 4, R * P.S},         {"action", h->er.act, 4, R * P.A},
       {"reward", h->er.rew, 4, R},             {"environment_id", h->er.env, 4, R},
@@ -2515,9 +2530,9 @@ bool vr_field(kg_vracer_t h, const char *name, VrField &f) {
       {"retrace", h->er.ret, 4, R},            {"importance_weight", h->er.iw, 4, R},
       {"truncated_importance_weight", h->er.tiw, 4, R}, {"truncated_state_value", h->er.tv, 4, R},
       {"on_policy", h->er.onp, 4, R},          {"episode_id", h->er.ep_id, 8, R},
-      {"episode_pos", h->er.ep_pos, 4, R},     {"hyperparameters", h->theta, 4, h->nuser},
-      {"adam_first_moment", h->m1, 4, h->nuser}, {"adam_second_moment", h->m2, 4, h->nuser},
-      {"gradient", h->grad, 4, h->nuser},      {"env_states", h->X, 4, E * P.S},
+      {"episode_pos", h->er.ep_pos, 4, R},     {"hyperparameters", h->theta, 4, h->nuser, true},
+      {"adam_first_moment", h->m1, 4, h->nuser, true}, {"adam_second_moment", h->m2, 4, h->nuser, true},
+      {"gradient", h->grad, 4, h->nuser, true}, {"env_states", h->X, 4, E * P.S},
       {"env_u", h->ev.u, 8, E * 4},            {"env_time", h->ev.time, 8, E},
       {"env_steps", h->ev.t, 4, E},
       {"env_ids", h->ev.env_id, 4, E},         {"env_sample_ids", h->ev.sample, 8, E},
@@ -2530,11 +2545,29 @@ bool vr_field(kg_vracer_t h, const char *name, VrField &f) {
       {"state_rescaling_means", &h->st->smean[0], 4, (size_t)std::min(P.S, MAXS)},
       {"state_rescaling_sigmas", &h->st->ssdev[0], 4, (size_t)std::min(P.S, MAXS)},
       {"meta_phase_ticks", &h->st->mtr[0], 8, (size_t)9},
+      // the last update's intermediates, device layout (hidden width padded to
+      // the scalar "padded_hidden_size"; padded columns are exactly 0):
+      // activations[l] = layer l's output, rowsMax rows of which the update
+      // fills 2B (mini-batch states, then their truncated states).  The hidden
+      // gradients are those with respect to a layer's pre-activation, ping-pong:
+      // the last hidden layer's (L-1) goes to hidden_gradient_a, layer L-2's
+      // to _b, L-3's to _a again, ...; after an update _a holds layer 0's when
+      // L is odd and layer 1's when L is even, _b (L >= 2) the other of the two.
+      {"mini_batch_states", h->Xmb, 4, 2 * B * P.S},
+      {"activations", h->acts, 4, (size_t)P.L * h->rowsMax * H},
+      {"output_layer_gradient", h->dZ, 4, B * P.O},
+      {"hidden_gradient_a", h->dHa, 4, B * H},
+      {"hidden_gradient_b", h->dHb, 4, B * H},
+      // the hyperparameter-shaped arrays as the device holds them (padded
+      // width, [W (out x in), b] per layer): the padded entries are exactly 0
+      {"device_hyperparameters", h->theta, 4, h->nparam},
+      {"device_gradient", h->grad, 4, h->nparam},
+      {"device_adam_first_moment", h->m1, 4, h->nparam},
+      {"device_adam_second_moment", h->m2, 4, h->nparam},
   };
   for (auto &x : tab)
     if (!strcmp(x.n, name)) {
-      f = VrField{x.p, x.elem, x.count,
-                  x.p == h->theta || x.p == h->grad || x.p == h->m1 || x.p == h->m2};
+      f = VrField{x.p, x.elem, x.count, x.param};
       return true;
     }
   return false;
@@ -2840,7 +2873,7 @@ static const char *const kScalarNames[] = {"learning_rate", "refer_beta", "off_p
                                            "policy_update_count", "total", "size", "current_episode",
                                            "current_sample_id", "mini_batch_counter", "environment_step",
                                            "step_new_experiences", "step_episodes", "experience_count",
-                                           "step_reward_sum"};
+                                           "step_reward_sum", "padded_hidden_size"};
 
 int kg_vracer_get_scalar(kg_vracer_t h, const char *name, double *v) {
   KG_CHECK(h && name && v, "vracer: null argument");
@@ -2850,7 +2883,8 @@ int kg_vracer_get_scalar(kg_vracer_t h, const char *name, double *v) {
   const double vals[] = {s.lr, s.beta, s.cutoff, s.off_ratio, s.eta, s.b1p, s.b2p, (double)s.off_count,
                          (double)s.update_count, (double)s.total, (double)s.size, (double)s.episode,
                          (double)s.sample_id, (double)s.mb_counter, (double)s.env_step, (double)s.step_new,
-                         (double)s.step_episodes, (double)s.experience_count, s.step_reward_sum};
+                         (double)s.step_episodes, (double)s.experience_count, s.step_reward_sum,
+                         (double)h->P.H};
   for (size_t i = 0; i < sizeof(vals) / sizeof(vals[0]); i++)
     if (!strcmp(kScalarNames[i], name)) {
       *v = vals[i];
@@ -3089,8 +3123,7 @@ static bool vr_draw_ahead() {
 static int vr_graph_len(const Params &P) {
   const char *e = getenv("KORALI_AMD_VR_GRAPH");
   const int n = e ? atoi(e) : 64;
-  const char *fe = getenv("KORALI_AMD_VR_FUSED");
-  if (P.H <= 256 && fe && *fe == '1') return 0;
+  if (vr_fused(P)) return 0;
   return n < 0 ? 0 : n > 256 ? 256 : n;
 }
 

@@ -348,6 +348,123 @@ int kg_dea_windows(kg_dea_t h, size_t *last_windows, size_t *window_words);
 int kg_dea_profile(kg_dea_t h, int enable);
 int kg_dea_profile_read(kg_dea_t h, const char *stage, double *ms_total, size_t *count);
 
+/* ------------------------------------------------------------- MOCMAES */
+/* Optimizer/MOCMAES (multi-objective CMA-ES), bit-exact to MOCMAES.cpp.base:
+ *
+ *   kg_mocmaes_initialize     MOCMAES::setInitialConfiguration  MOCMAES.cpp.base:10-140
+ *   kg_mocmaes_prepare        MOCMAES::prepareGeneration        MOCMAES.cpp.base:172-184
+ *                             (sampleSingle :186-228: parent pick :188-195,
+ *                              gsl_linalg_cholesky_decomp1 + gsl_matrix_scale :198-207,
+ *                              Multivariate Normal::getRandomVector
+ *                              multivariate/normal/normal.cpp.base:30-35 until
+ *                              Optimizer::isSampleFeasible optimizer.cpp.base:5-14 holds :209-217)
+ *   kg_mocmaes_eval_builtin   Optimization::evaluateMultiple → user objective
+ *                             optimization.cpp.base:36-45, batched over P
+ *   kg_mocmaes_get_candidates / kg_mocmaes_set_values
+ *                             KORALI_START/WAITALL/GET of MOCMAES::runGeneration
+ *                             MOCMAES.cpp.base:148-166 (host-callback objectives)
+ *   kg_mocmaes_update         MOCMAES::updateDistribution       MOCMAES.cpp.base:334-408
+ *                             (sortSampleIndices :230-332) and
+ *                             MOCMAES::updateStatistics         MOCMAES.cpp.base:410-520
+ *   kg_mocmaes_generation     MOCMAES::runGeneration            MOCMAES.cpp.base:142-170
+ *   kg_mocmaes_{get,set}_field / _{get,set}_rng
+ *                             Module::getConfiguration / setConfiguration of the
+ *                             solver state incl. RNG "Range" (distribution.cpp.base:10-62)
+ *
+ * Limits (MOCMAES): N <= 128 (a parent's factor is kept in LDS),
+ * N <= P (updateStatistics reads _currentSigma[d] for d < N, :455: out of
+ * bounds in the reference otherwise), 2 <= K <= 8.
+ * A parent covariance with a non-positive Cholesky pivot is an error here
+ * (kg_last_error); the reference ignores gsl_linalg_cholesky_decomp1's status
+ * (:203-206) and draws from the partially factored matrix.
+ * "Infeasible Sample Count" stays 0: the reference's increment is commented
+ * out (:215). */
+typedef struct kg_mocmaes_s *kg_mocmaes_t;
+
+enum kg_mocmaes_parent_order {
+  KG_MOCMAES_PARENTS_DESCENDING = 0, /* slot values.size() - sortedIndices[i] - 1 (MOCMAES.cpp.base:385) */
+  KG_MOCMAES_PARENTS_RECORDED = 1    /* the slot order of the reference's committed 2021 result files
+                                        (tests/python/plot/mocmaes): ascending index of the merged
+                                        population; not a Korali setting */
+};
+
+/* builtin objective kernels (examples/optimization/multiobjective/_model/model.py) */
+enum kg_mocmaes_objective {
+  KG_MOCMAES_OBJ_ROSENBROCK_SPHERE = 0,     /* negative_rosenbrock_and_sphere, K = 2 */
+  KG_MOCMAES_OBJ_ROSENBROCK_TWO_SPHERES = 1 /* negative_rosenbrock_and_two_spheres, K = 3 */
+};
+
+typedef struct {
+  size_t variable_count;     /* N, 1..128 and <= population size */
+  size_t population_size;    /* P ("Population Size"; 0 → ceil(4 + floor(3 log N)), :24) */
+  size_t mu_value;           /* "Mu Value" (0 → P / 2, :25), <= P */
+  size_t num_objectives;     /* K ("Num Objectives"), 2..8 */
+  const double *lower_bound; /* N (may be infinite where value and deviation are given) */
+  const double *upper_bound; /* N */
+  const double *initial_value; /* N or NULL; non-finite → inferred from finite bounds (:73-78).  The
+                                  reference never reads it again: the parents start at 0 (:119) */
+  const double *initial_sdev;  /* N or NULL; non-finite → 0.3 (upper - lower) (:80-85) */
+  double evolution_path_adaption_strength; /* < 0 → 2 / (N + 2) (:127) */
+  double covariance_learning_rate;         /* < 0 → 2 / (N^2 + 6) (:128) */
+  double target_success_rate;              /* "Target Success Rate", (0, 1] */
+  double success_learning_rate;            /* "Success Learning Rate", (0, 1] */
+  int parent_order;          /* enum kg_mocmaes_parent_order */
+  uint64_t multinormal_seed; /* seed of the Multinormal generator (GSL mt19937) */
+  uint64_t uniform_seed;     /* seed of the Uniform generator */
+  size_t window_blocks;      /* blocks of N normals the draw sees per launch; at least P + 64 */
+  size_t max_windows;        /* windows one kg_mocmaes_prepare may use before it reports a sample that
+                                never becomes feasible; 0 → 1024.  Not a reference setting: the
+                                reference redraws forever there. */
+  size_t archive_rows;       /* first capacity of the "Sample Collection" buffers (grown on demand);
+                                0 → max(4 P, 1024) */
+  int device;                /* HIP device ordinal */
+} kg_mocmaes_cfg;
+
+/* Every entry checks its arguments, and create its configuration, before the
+ * device is touched. */
+int kg_mocmaes_create(const kg_mocmaes_cfg *cfg, kg_mocmaes_t *out);
+int kg_mocmaes_destroy(kg_mocmaes_t h);
+int kg_mocmaes_initialize(kg_mocmaes_t h);
+/* Previous* = Current* (a buffer swap) and the P draws of `generation`
+ * (generation 1 initializes a fresh handle first).  Blocks until the draw
+ * chain is through (one small device read per window).  The offspring's
+ * covariance, sigma, path and success rate are written by kg_mocmaes_update. */
+int kg_mocmaes_prepare(kg_mocmaes_t h, size_t generation);
+int kg_mocmaes_eval_builtin(kg_mocmaes_t h, int objective); /* enum kg_mocmaes_objective; "Model Evaluation Count" += P */
+int kg_mocmaes_get_candidates(kg_mocmaes_t h, double *X, size_t ld);
+int kg_mocmaes_set_values(kg_mocmaes_t h, const double *V); /* P x K row-major, finite; "Model Evaluation Count" += P */
+int kg_mocmaes_update(kg_mocmaes_t h, size_t generation);
+int kg_mocmaes_generation(kg_mocmaes_t h, size_t generation, int objective);
+int kg_mocmaes_synchronize(kg_mocmaes_t h); /* waits and reports device-side errors */
+/* named state fields, keys as in MOCMAES.config's Internal Settings: {Current,
+ * Previous, Parent} x {"Sample Population", "Sigma", "Covariance Matrix",
+ * "Evolution Paths", "Success Probabilities"}, "Current Values", "Previous
+ * Values", "Parent Index", {"Best Ever", "Previous Best", "Current Best"} x
+ * {"Values", "Variables Vector"}, "Current Best Value Differences", "Current
+ * Best Variable Differences", "Current Min Standard Deviations", "Current Max
+ * Standard Deviations", "Sample Collection", "Sample Value Collection";
+ * scalars "Current Non Dominated Sample Count", "Infeasible Sample Count",
+ * "Finished Sample Count", "Model Evaluation Count"; sizes in doubles.
+ * Setting "Sample Collection" sets the archive's row count; "Sample Value
+ * Collection" follows with the same rows. */
+int kg_mocmaes_field_size(kg_mocmaes_t h, const char *name, size_t *n);
+int kg_mocmaes_get_field(kg_mocmaes_t h, const char *name, double *out, size_t n);
+int kg_mocmaes_set_field(kg_mocmaes_t h, const char *name, const double *in, size_t n);
+/* 5000-byte GSL states as for CMA-ES.  which: 0 Multinormal, 1 Uniform generator. */
+int kg_mocmaes_get_rng(kg_mocmaes_t h, int which, void *state5000);
+int kg_mocmaes_set_rng(kg_mocmaes_t h, int which, const void *state5000);
+/* Diagnostics only (holds no solver state; any pointer may be NULL): windows
+ * the last prepare used and the window size in blocks, the archive buffers'
+ * capacity in rows, and the rank-peeling rounds the last multi-workgroup sort
+ * counted (0 after a one-workgroup sort).  The tests read them to see that
+ * the relaunch, growth and multi-workgroup paths ran. */
+int kg_mocmaes_diagnostics(kg_mocmaes_t h, size_t *last_windows, size_t *window_blocks, size_t *archive_capacity,
+                           size_t *last_rounds);
+/* stage timing as kg_cmaes_profile; stages "draw", "evaluate", "sort",
+ * "update", "parents", "statistics" */
+int kg_mocmaes_profile(kg_mocmaes_t h, int enable);
+int kg_mocmaes_profile_read(kg_mocmaes_t h, const char *stage, double *ms_total, size_t *count);
+
 /* ------------------------------------------------------------ testing */
 /* Host reference of the mt19937 jump-ahead the chunked device producer
  * uses: out = the 624 untempered words `distance` positions after window624

@@ -6,6 +6,7 @@
 #include "kg_eigen.hip"
 #include "kg_cmaes.hip"
 #include "kg_dea.hip"
+#include "kg_mocmaes.hip"
 #include "kg_hier.hip"
 #include "kg_tmcmc.hip"
 #include "kg_vracer.hip"

@@ -542,6 +542,23 @@ const KeyList CMAES_KEYS = {
     "Covariance Update"};
 const KeyList CMAES_TERMINATION = {"Max Infeasible Resamplings", "Max Condition Covariance Matrix",
                                    "Min Standard Deviation", "Max Standard Deviation"};
+// MOCMAES.config
+const KeyList MOCMAES_KEYS = {
+    // Configuration Settings
+    "Population Size", "Mu Value", "Evolution Path Adaption Strength", "Covariance Learning Rate",
+    "Target Success Rate", "Threshold Probability", "Success Learning Rate",
+    // Internal Settings
+    "Num Objectives", "Multinormal Generator", "Uniform Generator", "Current Non Dominated Sample Count",
+    "Current Values", "Previous Values", "Parent Index", "Parent Sample Population", "Current Sample Population",
+    "Previous Sample Population", "Parent Sigma", "Current Sigma", "Previous Sigma", "Parent Covariance Matrix",
+    "Current Covariance Matrix", "Previous Covariance Matrix", "Parent Evolution Paths", "Current Evolution Paths",
+    "Previous Evolution Paths", "Parent Success Probabilities", "Current Success Probabilities",
+    "Previous Success Probabilities", "Finished Sample Count", "Best Ever Values", "Best Ever Variables Vector",
+    "Previous Best Values", "Previous Best Variables Vector", "Current Best Values", "Current Best Variables Vector",
+    "Sample Collection", "Sample Value Collection", "Infeasible Sample Count", "Current Best Value Differences",
+    "Current Best Variable Differences", "Current Min Standard Deviations", "Current Max Standard Deviations"};
+const KeyList MOCMAES_TERMINATION = {"Min Max Value Difference Threshold", "Min Variable Difference Threshold",
+                                     "Min Standard Deviation", "Max Standard Deviation"};
 const KeyList TMCMC_KEYS = {
     // Configuration Settings (TMCMC.config)
     "Version", "Population Size", "Max Chain Length", "Burn In", "Per Generation Burn In",
@@ -1509,6 +1526,312 @@ struct CmaesModule : SolverModule {
   }
 
   std::string type() const override { return "Optimizer/CMAES"; }
+};
+
+// ------------------------------------------------------------- MOCMAES
+// MOCMAES.cpp.base on the device (kg_mocmaes_*); state names as in
+// MOCMAES.config.  {field, row length selector}: 'N' rows of N, 'C' rows of
+// N*N, 'K' rows of K, '1' a flat vector.
+struct MocmaesFieldSpec {
+  const char *name;
+  char row;
+};
+const MocmaesFieldSpec MOCMAES_FIELDS[] = {
+    {"Current Values", 'K'},
+    {"Previous Values", 'K'},
+    {"Parent Sample Population", 'N'},
+    {"Current Sample Population", 'N'},
+    {"Previous Sample Population", 'N'},
+    {"Parent Sigma", '1'},
+    {"Current Sigma", '1'},
+    {"Previous Sigma", '1'},
+    {"Parent Covariance Matrix", 'C'},
+    {"Current Covariance Matrix", 'C'},
+    {"Previous Covariance Matrix", 'C'},
+    {"Parent Evolution Paths", 'N'},
+    {"Current Evolution Paths", 'N'},
+    {"Previous Evolution Paths", 'N'},
+    {"Parent Success Probabilities", '1'},
+    {"Current Success Probabilities", '1'},
+    {"Previous Success Probabilities", '1'},
+    {"Best Ever Values", '1'},
+    {"Best Ever Variables Vector", 'N'},
+    {"Previous Best Values", '1'},
+    {"Previous Best Variables Vector", 'N'},
+    {"Current Best Values", '1'},
+    {"Current Best Variables Vector", 'N'},
+    {"Sample Collection", 'N'},
+    {"Sample Value Collection", 'K'},
+    {"Current Best Value Differences", '1'},
+    {"Current Best Variable Differences", '1'},
+    {"Current Min Standard Deviations", '1'},
+    {"Current Max Standard Deviations", '1'}};
+const char *MOCMAES_COUNTS[] = {"Current Non Dominated Sample Count", "Infeasible Sample Count",
+                                "Finished Sample Count", "Model Evaluation Count"};
+
+struct MocmaesModule : SolverModule {
+  kg_mocmaes_t h = nullptr;
+  size_t N = 0, P = 0, mu = 0, K = 0;
+  int objective = -1;  // builtin kernel, or -1: host function
+  size_t fn = 0;
+  double maxGenerations, maxModelEvaluations, maxValue, minValueDiff;
+  double minVariableDiff, minStd, maxStd;
+  double cc, ccov, target, threshold, cp;
+
+  ~MocmaesModule() override {
+    if (h) kg_mocmaes_destroy(h);
+  }
+
+  MocmaesModule(Json &js, Seeder &seeds, bool resume, Collective *dist) {
+    Json &sv = js["Solver"];
+    Json &pb = js["Problem"];
+    const std::string pt = canon(str(pb, "Type", ""));
+    if (pt != "optimization")  // MOCMAES.cpp.base:15-17
+      fail("Korali problem incompatible with MO-CMAES, must be of type 'Optimization'.\n");
+    if (dist)
+      fail("Optimizer/MOCMAES does not shard across ranks: the Distributed conduit is not provided for this solver "
+           "(Sequential or Concurrent).");
+    rejectUnrecognised(sv, "MOCMAES", {SOLVER_KEYS, OPTIMIZER_KEYS, MOCMAES_KEYS},
+                       {SOLVER_TERMINATION, OPTIMIZER_TERMINATION, MOCMAES_TERMINATION});
+    rejectProblemUnrecognised(pb, pt);
+    const std::vector<VariableSpec> vars = readVariables(js);
+    N = vars.size();
+    K = uint(pb, "Num Objectives", 1);
+    if (K < 2) fail("Problem requires multiple objectives, 'Num Objectives' is set to %zu\n.", K);  // :20-21
+    P = uint(sv, "Population Size", 0);
+    mu = uint(sv, "Mu Value", 0);
+    // setInitialConfiguration :24-27
+    if (P == 0) P = (size_t)std::ceil(4. + std::floor(3. * std::log((double)N)));
+    if (mu == 0) mu = (size_t)(P / 2.);
+    if (mu > P)
+      fail("Number of parents ('Mu Value' %zu) must be smaller or equal with population size (%zu).\n", mu, P);
+    cc = num(sv, "Evolution Path Adaption Strength", -1.0);
+    ccov = num(sv, "Covariance Learning Rate", -1.0);
+    target = num(sv, "Target Success Rate", 0.175);
+    threshold = num(sv, "Threshold Probability", 0.44);
+    cp = num(sv, "Success Learning Rate", 0.08);
+    Json &tc = sv["Termination Criteria"];
+    maxGenerations = num(tc, "Max Generations", 1e10);
+    maxModelEvaluations = num(tc, "Max Model Evaluations", 1e9);
+    maxValue = num(tc, "Max Value", INFINITY);
+    minValueDiff = num(tc, "Min Value Difference Threshold", -INFINITY);
+    // accepted and written back, but never read: the criterion of that name
+    // tests the optimizer base's 'Min Value Difference Threshold' (MOCMAES.config:54)
+    (void)num(tc, "Min Max Value Difference Threshold", -INFINITY);
+    minVariableDiff = num(tc, "Min Variable Difference Threshold", -INFINITY);
+    minStd = num(tc, "Min Standard Deviation", -INFINITY);
+    maxStd = num(tc, "Max Standard Deviation", INFINITY);
+    if (pb.contains("Objective Kernel")) {
+      std::string k = canon(pb["Objective Kernel"].getString());
+      k.erase(std::remove(k.begin(), k.end(), '_'), k.end());
+      objective = k == "negativerosenbrockandsphere"       ? KG_MOCMAES_OBJ_ROSENBROCK_SPHERE
+                  : k == "negativerosenbrockandtwospheres" ? KG_MOCMAES_OBJ_ROSENBROCK_TWO_SPHERES
+                                                           : -2;
+      if (objective == -2)
+        fail("Unknown multi-objective 'Objective Kernel' '%s' (negative_rosenbrock_and_sphere, "
+             "negative_rosenbrock_and_two_spheres).", pb["Objective Kernel"].getString().c_str());
+      const size_t need = objective == KG_MOCMAES_OBJ_ROSENBROCK_SPHERE ? 2 : 3;
+      if (K != need)
+        fail("'Objective Kernel' '%s' has %zu objectives, 'Num Objectives' is %zu.",
+             pb["Objective Kernel"].getString().c_str(), need, K);
+    } else {
+      if (!pb.contains("Objective Function")) fail("Problem 'Optimization' requires an 'Objective Function'.");
+      fn = pb["Objective Function"].getUInt();
+    }
+    std::vector<double> lb(N), ub(N), iv(N), istd(N);
+    for (size_t i = 0; i < N; i++) {
+      lb[i] = vars[i].lb;
+      ub[i] = vars[i].ub;
+      iv[i] = vars[i].iv;
+      istd[i] = vars[i].istd;
+    }
+    // generators in MOCMAES.config Internal Settings order: Multinormal, Uniform
+    Json &gn = sv["Multinormal Generator"], &gu = sv["Uniform Generator"];
+    gn["Type"] = "Multivariate/Normal";
+    gu["Type"] = "Univariate/Uniform";
+    gu["Minimum"] = 0.0;
+    gu["Maximum"] = 1.0;
+    kg_mocmaes_cfg c{};
+    c.variable_count = N;
+    c.population_size = P;
+    c.mu_value = mu;
+    c.num_objectives = K;
+    c.lower_bound = lb.data();
+    c.upper_bound = ub.data();
+    c.initial_value = iv.data();
+    c.initial_sdev = istd.data();
+    c.evolution_path_adaption_strength = cc;
+    c.covariance_learning_rate = ccov;
+    c.target_success_rate = target;
+    c.success_learning_rate = cp;
+    c.parent_order = KG_MOCMAES_PARENTS_DESCENDING;
+    c.multinormal_seed = seeds.assign(gn);
+    c.uniform_seed = seeds.assign(gu);
+    c.device = solverDevice(js, nullptr);
+    check(kg_mocmaes_create(&c, &h));
+    // :127-128
+    if (cc < 0.) cc = 2. / (N + 2.);
+    if (ccov < 0.) ccov = 2. / (N * N + 6.);
+    try {  // (the destructor of a partly constructed object does not run)
+      unsigned char st[5000];
+      if (seeds.range(gn, st)) check(kg_mocmaes_set_rng(h, 0, st));
+      if (seeds.range(gu, st)) check(kg_mocmaes_set_rng(h, 1, st));
+      if (resume) restore(sv);
+    } catch (...) {
+      kg_mocmaes_destroy(h);
+      h = nullptr;
+      throw;
+    }
+  }
+
+  // MOCMAES::setConfiguration of a saved state (loadState + resume).  A saved
+  // field of the wrong size is an error (kg_mocmaes_set_field checks it; the
+  // archive's row count comes with 'Sample Collection'), not a silent default.
+  void restore(Json &sv) {
+    check(kg_mocmaes_initialize(h));
+    for (const MocmaesFieldSpec &f : MOCMAES_FIELDS)
+      if (sv.contains(f.name) && sv[f.name].is_array()) {
+        std::vector<double> v = flatten(sv[f.name]);
+        if (kg_mocmaes_set_field(h, f.name, v.data(), v.size()) != 0)
+          fail("Resuming Optimizer/MOCMAES: saved field '%s' has %zu values: %s", f.name, v.size(), kg_last_error());
+      }
+    if (sv.contains("Parent Index") && sv["Parent Index"].is_array()) {
+      std::vector<double> v = flatten(sv["Parent Index"]);
+      if (kg_mocmaes_set_field(h, "Parent Index", v.data(), v.size()) != 0)
+        fail("Resuming Optimizer/MOCMAES: saved field 'Parent Index' has %zu values: %s", v.size(), kg_last_error());
+    }
+    for (const char *k : MOCMAES_COUNTS)
+      if (sv.contains(k) && sv[k].is_number()) {
+        const double v = sv[k].getDouble();
+        check(kg_mocmaes_set_field(h, k, &v, 1));
+      }
+  }
+
+  // Optimization::evaluateMultiple for one sample (optimization.cpp.base:36-45)
+  void evaluateSample(size_t gen, size_t i, const std::vector<double> &X, std::vector<double> &V, Function &f) {
+    Sample s;
+    s["Module"] = "Problem";
+    s["Operation"] = "Evaluate Multiple";
+    s["Sample Id"] = (unsigned long long)i;
+    s["Current Generation"] = (unsigned long long)gen;
+    s["Parameters"] = std::vector<double>(X.begin() + i * N, X.begin() + (i + 1) * N);
+    f(s);
+    if (!s.contains("F(x)")) fail("The objective function did not assign 'F(x)' for sample %zu.", i);
+    const std::vector<double> v = KORALI_GET(std::vector<double>, s, "F(x)");
+    if (v.size() != K)
+      fail("The objective function returned %zu values in 'F(x)' for sample %zu, 'Num Objectives' is %zu.", v.size(), i,
+           K);
+    for (size_t k = 0; k < K; k++) {
+      if (!std::isfinite(v[k]))
+        fail("Non finite value of function evaluation detected for variable %lu: %f\n", (unsigned long)k, v[k]);
+      V[i * K + k] = v[k];
+    }
+  }
+
+  void runGeneration(size_t gen) override {
+    check(kg_mocmaes_prepare(h, gen));  // (generation 1 runs setInitialConfiguration first, :144)
+    if (objective >= 0) {
+      check(kg_mocmaes_eval_builtin(h, objective));
+    } else {
+      // KORALI_START every sample, KORALI_WAITALL (:148-166)
+      std::vector<double> X(P * N), V(P * K);
+      check(kg_mocmaes_get_candidates(h, X.data(), N));
+      Function &f = getFunction(fn);
+      conduit->evaluateBatch(P, [&](size_t i) { evaluateSample(gen, i, X, V, f); });
+      check(kg_mocmaes_set_values(h, V.data()));
+    }
+    check(kg_mocmaes_update(h, gen));
+  }
+
+  std::vector<double> vector(const char *k) {
+    size_t n = 0;
+    check(kg_mocmaes_field_size(h, k, &n));
+    std::vector<double> v(n);
+    check(kg_mocmaes_get_field(h, k, v.data(), n));
+    return v;
+  }
+
+  void checkTermination(size_t gen, std::vector<std::string> &met) override {
+    check(kg_mocmaes_synchronize(h));  // device-side errors of the last generation
+    if (gen > maxGenerations) met.push_back("Max Generations");
+    if (maxModelEvaluations <= vector("Model Evaluation Count")[0]) met.push_back("Max Model Evaluations");
+    if (gen <= 1) return;
+    // the optimizer base criteria as setInitialConfiguration leaves them
+    // (:63-65): _currentBestValue = +Inf, _previousBestValue = -Inf, and
+    // _bestEverValue stays at its default -Inf (optimizer.config)
+    if (-INFINITY > maxValue) met.push_back("Max Value");
+    if (std::fabs(INFINITY - (-INFINITY)) < minValueDiff) met.push_back("Min Value Difference Threshold");
+    // MOCMAES.config:52-72
+    const std::vector<double> dv = vector("Current Best Value Differences"),
+                              dx = vector("Current Best Variable Differences"),
+                              mn = vector("Current Min Standard Deviations"),
+                              mx = vector("Current Max Standard Deviations");
+    // :54 as written: against _minValueDifferenceThreshold, the base's 'Min Value
+    // Difference Threshold'; 'Min Max Value Difference Threshold' itself is unread
+    if (std::fabs(*std::max_element(dv.begin(), dv.end())) < minValueDiff)
+      met.push_back("Min Max Value Difference Threshold");
+    if (*std::max_element(dx.begin(), dx.end()) < minVariableDiff) met.push_back("Min Variable Difference Threshold");
+    if (*std::max_element(mn.begin(), mn.end()) <= minStd) met.push_back("Min Standard Deviation");
+    if (*std::min_element(mx.begin(), mx.end()) >= maxStd) met.push_back("Max Standard Deviation");
+  }
+
+  void getConfiguration(Json &sv) override {
+    for (const MocmaesFieldSpec &f : MOCMAES_FIELDS) {
+      const std::vector<double> v = vector(f.name);
+      const size_t cols = f.row == 'N' ? N : f.row == 'C' ? N * N : f.row == 'K' ? K : 0;
+      if (cols)
+        sv[f.name] = matrixJson(v, v.size() / cols, cols);
+      else
+        sv[f.name] = v;
+    }
+    {
+      const std::vector<double> v = vector("Parent Index");
+      Json a = Json::array();
+      for (double x : v) a.push_back((unsigned long long)x);
+      sv["Parent Index"] = a;
+    }
+    for (const char *k : MOCMAES_COUNTS) sv[k] = (unsigned long long)vector(k)[0];
+    sv["Variable Count"] = (unsigned long long)N;
+    sv["Num Objectives"] = (unsigned long long)K;
+    sv["Population Size"] = (unsigned long long)P;
+    sv["Mu Value"] = (unsigned long long)mu;
+    sv["Evolution Path Adaption Strength"] = cc;
+    sv["Covariance Learning Rate"] = ccov;
+    sv["Target Success Rate"] = target;
+    sv["Threshold Probability"] = threshold;
+    sv["Success Learning Rate"] = cp;
+    // the optimizer base's values (:63-65)
+    sv["Current Best Value"] = INFINITY;
+    sv["Previous Best Value"] = -INFINITY;
+    sv["Best Ever Value"] = -INFINITY;
+    unsigned char st[5000];
+    check(kg_mocmaes_get_rng(h, 0, st));
+    sv["Multinormal Generator"]["Range"] = hexState(st);
+    check(kg_mocmaes_get_rng(h, 1, st));
+    sv["Uniform Generator"]["Range"] = hexState(st);
+  }
+
+  // MOCMAES::finalize (:537-541)
+  void finalize(Json &js) override {
+    const std::vector<double> v = vector("Sample Value Collection"), x = vector("Sample Collection");
+    js["Results"]["Pareto Optimal Samples"]["F(x)"] = matrixJson(v, v.size() / K, K);
+    js["Results"]["Pareto Optimal Samples"]["Parameters"] = matrixJson(x, x.size() / N, N);
+  }
+
+  // printGenerationAfter (:524-535)
+  void printAfter(const Logger &log) override {
+    const std::vector<double> cur = vector("Current Best Values"), best = vector("Best Ever Values"),
+                              mn = vector("Current Min Standard Deviations"),
+                              mx = vector("Current Max Standard Deviations");
+    log.log(2, "Current Function Values = (Max, Best):\n");
+    for (size_t k = 0; k < K; k++) log.log(2, "                              = (%+6.3e, %+6.3e)\n", cur[k], best[k]);
+    log.log(2, "Standard Devs:            Min = %+6.3e - Max = %+6.3e\n", *std::min_element(mn.begin(), mn.end()),
+            *std::max_element(mx.begin(), mx.end()));
+    log.log(2, "Non Dominated Samples:   Current = %zu - Overall = %zu\n",
+            (size_t)vector("Current Non Dominated Sample Count")[0], vector("Sample Collection").size() / N);
+  }
+
+  std::string type() const override { return "Optimizer/MOCMAES"; }
 };
 
 // --------------------------------------------------------------- TMCMC
@@ -2834,6 +3157,8 @@ void runExperiment(Experiment &e, Conduit &conduit) {
   } release{st};
   if (stype == "optimizer/cmaes" || stype == "cmaes") {
     st.solver.reset(new CmaesModule(js, seeds, resume, dist));
+  } else if (stype == "optimizer/mocmaes" || stype == "mocmaes") {
+    st.solver.reset(new MocmaesModule(js, seeds, resume, dist));
   } else if (stype == "sampler/tmcmc" || stype == "tmcmc") {
     tm = new TmcmcModule(js, seeds, distSeeds, distStates, resume, dist);
     st.solver.reset(tm);
@@ -2845,8 +3170,8 @@ void runExperiment(Experiment &e, Conduit &conduit) {
            "conduit (independent replicas).");
     st.solver.reset(new VracerModule(js, seeds, resume));
   } else {
-    fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Sampler/TMCMC and "
-         "Agent/Continuous/VRACER).",
+    fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Optimizer/MOCMAES, Sampler/TMCMC "
+         "and Agent/Continuous/VRACER).",
          sv["Type"].getString().c_str());
   }
   clk.mark("setup");

@@ -104,6 +104,22 @@ DEA_MUTATION_RULES = {"fixed": 0, "self adaptive": 1}
 DEA_PARENT_RULES = {"random": 0, "best": 1}
 DEA_ACCEPT_RULES = {"best": 0, "greedy": 1, "iterative": 2, "improved": 3}
 
+class _MocmaesCfg(C.Structure):
+    _fields_ = [
+        ("variable_count", C.c_size_t), ("population_size", C.c_size_t), ("mu_value", C.c_size_t),
+        ("num_objectives", C.c_size_t),
+        ("lower_bound", C.POINTER(C.c_double)), ("upper_bound", C.POINTER(C.c_double)),
+        ("initial_value", C.POINTER(C.c_double)), ("initial_sdev", C.POINTER(C.c_double)),
+        ("evolution_path_adaption_strength", C.c_double), ("covariance_learning_rate", C.c_double),
+        ("target_success_rate", C.c_double), ("success_learning_rate", C.c_double), ("parent_order", C.c_int),
+        ("multinormal_seed", C.c_uint64), ("uniform_seed", C.c_uint64), ("window_blocks", C.c_size_t),
+        ("max_windows", C.c_size_t), ("archive_rows", C.c_size_t), ("device", C.c_int),
+    ]
+
+
+MOCMAES_PARENT_ORDERS = {"descending": 0, "recorded": 1}
+MOCMAES_OBJECTIVES = {"negative_rosenbrock_and_sphere": 0, "negative_rosenbrock_and_two_spheres": 1}
+
 EXPORTED = [
     "kg_last_error", "kg_abi_version", "kg_device_count",
     "kg_cmaes_create", "kg_cmaes_destroy", "kg_cmaes_initialize", "kg_cmaes_sample", "kg_cmaes_eval_builtin",
@@ -119,6 +135,11 @@ EXPORTED = [
     "kg_dea_get_candidates", "kg_dea_set_fitness", "kg_dea_update", "kg_dea_generation", "kg_dea_synchronize",
     "kg_dea_field_size", "kg_dea_get_field", "kg_dea_set_field", "kg_dea_get_rng", "kg_dea_set_rng",
     "kg_dea_windows", "kg_dea_profile", "kg_dea_profile_read",
+    "kg_mocmaes_create", "kg_mocmaes_destroy", "kg_mocmaes_initialize", "kg_mocmaes_prepare",
+    "kg_mocmaes_eval_builtin", "kg_mocmaes_get_candidates", "kg_mocmaes_set_values", "kg_mocmaes_update",
+    "kg_mocmaes_generation", "kg_mocmaes_synchronize", "kg_mocmaes_field_size", "kg_mocmaes_get_field",
+    "kg_mocmaes_set_field", "kg_mocmaes_get_rng", "kg_mocmaes_set_rng", "kg_mocmaes_diagnostics",
+    "kg_mocmaes_profile", "kg_mocmaes_profile_read",
     "kg_tmcmc_create", "kg_tmcmc_destroy", "kg_tmcmc_generation", "kg_tmcmc_synchronize", "kg_tmcmc_field_size",
     "kg_tmcmc_get_field", "kg_tmcmc_set_field", "kg_tmcmc_get_rng", "kg_tmcmc_set_rng", "kg_tmcmc_prepare",
     "kg_tmcmc_evaluate", "kg_tmcmc_process", "kg_tmcmc_advance", "kg_tmcmc_get_pending",
@@ -204,6 +225,23 @@ def lib():
         L.kg_dea_windows.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
         L.kg_dea_profile.argtypes = [vp, ip]
         L.kg_dea_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
+        L.kg_mocmaes_create.argtypes = [C.POINTER(_MocmaesCfg), C.POINTER(vp)]
+        for f in ("kg_mocmaes_destroy", "kg_mocmaes_initialize", "kg_mocmaes_synchronize"):
+            getattr(L, f).argtypes = [vp]
+        for f in ("kg_mocmaes_prepare", "kg_mocmaes_update"):
+            getattr(L, f).argtypes = [vp, sz]
+        L.kg_mocmaes_eval_builtin.argtypes = [vp, ip]
+        L.kg_mocmaes_generation.argtypes = [vp, sz, ip]
+        L.kg_mocmaes_get_candidates.argtypes = [vp, dp, sz]
+        L.kg_mocmaes_set_values.argtypes = [vp, dp]
+        L.kg_mocmaes_field_size.argtypes = [vp, cp, C.POINTER(sz)]
+        L.kg_mocmaes_get_field.argtypes = [vp, cp, dp, sz]
+        L.kg_mocmaes_set_field.argtypes = [vp, cp, dp, sz]
+        L.kg_mocmaes_get_rng.argtypes = [vp, ip, vp]
+        L.kg_mocmaes_set_rng.argtypes = [vp, ip, vp]
+        L.kg_mocmaes_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 4
+        L.kg_mocmaes_profile.argtypes = [vp, ip]
+        L.kg_mocmaes_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_tmcmc_create.argtypes = [C.POINTER(_TmcmcCfg), C.POINTER(vp)]
         for f in ("kg_tmcmc_destroy", "kg_tmcmc_synchronize", "kg_tmcmc_evaluate", "kg_tmcmc_evaluate_prior"):
             getattr(L, f).argtypes = [vp]
@@ -593,6 +631,130 @@ class DeaDevice:
     def profile_read(self, stage):
         ms, n = C.c_double(), C.c_size_t()
         check(self._L.kg_dea_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
+class MocmaesDevice:
+    """One Optimizer/MOCMAES (multi-objective CMA-ES) instance on one MI355X
+    (kg_mocmaes_t), bit-exact to the reference's MOCMAES.cpp.base.  Generator
+    indices for rng_state / set_rng_state: 0 Multinormal, 1 Uniform.
+    parent_order "recorded" is the slot order of the reference's committed 2021
+    result files, not a Korali setting."""
+
+    def __init__(self, N, P, lower_bound, upper_bound, mu=0, num_objectives=2, initial_value=None, initial_sdev=None,
+                 evolution_path_adaption_strength=-1.0, covariance_learning_rate=-1.0, target_success_rate=0.175,
+                 success_learning_rate=0.08, parent_order="Descending", multinormal_seed=0, uniform_seed=0,
+                 window_blocks=0, max_windows=0, archive_rows=0, device=0):
+        L = lib()
+        self.N, self.K = int(N), int(num_objectives)
+        self._arrays = [_vec(lower_bound, self.N, np.nan), _vec(upper_bound, self.N, np.nan),
+                        _vec(initial_value, self.N, np.nan), _vec(initial_sdev, self.N, np.nan)]
+        cfg = _MocmaesCfg()
+        cfg.variable_count, cfg.population_size, cfg.mu_value = self.N, int(P), int(mu)
+        cfg.num_objectives = self.K
+        cfg.lower_bound, cfg.upper_bound, cfg.initial_value, cfg.initial_sdev = [_dptr(a) for a in self._arrays]
+        cfg.evolution_path_adaption_strength = float(evolution_path_adaption_strength)
+        cfg.covariance_learning_rate = float(covariance_learning_rate)
+        cfg.target_success_rate, cfg.success_learning_rate = float(target_success_rate), float(success_learning_rate)
+        cfg.parent_order = (MOCMAES_PARENT_ORDERS[parent_order.lower()] if isinstance(parent_order, str)
+                            else int(parent_order))
+        cfg.multinormal_seed = int(multinormal_seed) & (2**64 - 1)
+        cfg.uniform_seed = int(uniform_seed) & (2**64 - 1)
+        cfg.window_blocks, cfg.max_windows, cfg.archive_rows = int(window_blocks), int(max_windows), int(archive_rows)
+        cfg.device = int(device)
+        h = C.c_void_p()
+        check(L.kg_mocmaes_create(C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._L = L
+        # the defaults of setInitialConfiguration (MOCMAES.cpp.base:24-25)
+        self.P = int(P) or int(np.ceil(4. + np.floor(3. * np.log(float(self.N)))))
+        self.mu = int(mu) or int(self.P / 2.)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.kg_mocmaes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _objective(objective):
+        return MOCMAES_OBJECTIVES[objective.lower()] if isinstance(objective, str) else int(objective)
+
+    # stages
+    def initialize(self):
+        check(self._L.kg_mocmaes_initialize(self.h))
+
+    def prepare(self, generation):
+        check(self._L.kg_mocmaes_prepare(self.h, int(generation)))
+
+    def evaluate(self, objective):
+        check(self._L.kg_mocmaes_eval_builtin(self.h, self._objective(objective)))
+
+    def update(self, generation):
+        check(self._L.kg_mocmaes_update(self.h, int(generation)))
+
+    def generation(self, generation, objective):
+        check(self._L.kg_mocmaes_generation(self.h, int(generation), self._objective(objective)))
+
+    def synchronize(self):
+        check(self._L.kg_mocmaes_synchronize(self.h))
+
+    # host-callback objectives
+    def candidates(self):
+        X = np.empty((self.P, self.N))
+        check(self._L.kg_mocmaes_get_candidates(self.h, _dptr(X), self.N))
+        return X
+
+    def set_values(self, V):
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.shape != (self.P, self.K):
+            raise ValueError("value matrix has shape %s, expected (%d, %d)" % (V.shape, self.P, self.K))
+        check(self._L.kg_mocmaes_set_values(self.h, _dptr(V)))
+
+    # state
+    def field_size(self, name):
+        n = C.c_size_t()
+        check(self._L.kg_mocmaes_field_size(self.h, name.encode(), C.byref(n)))
+        return n.value
+
+    def __getitem__(self, name):
+        n = self.field_size(name)
+        out = np.empty(n)
+        check(self._L.kg_mocmaes_get_field(self.h, name.encode(), _dptr(out), n))
+        return out
+
+    def __setitem__(self, name, value):
+        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
+        check(self._L.kg_mocmaes_set_field(self.h, name.encode(), _dptr(a), a.size))
+
+    def rng_state(self, which=0):
+        buf = C.create_string_buffer(5000)
+        check(self._L.kg_mocmaes_get_rng(self.h, int(which), buf))
+        return buf.raw
+
+    def set_rng_state(self, state, which=0):
+        assert len(state) == 5000
+        buf = C.create_string_buffer(bytes(state), 5000)
+        check(self._L.kg_mocmaes_set_rng(self.h, int(which), buf))
+
+    def diagnostics(self):
+        """(windows the last prepare() used, window size in blocks, archive capacity in rows,
+        peeling rounds of the last multi-workgroup sort)"""
+        v = [C.c_size_t() for _ in range(4)]
+        check(self._L.kg_mocmaes_diagnostics(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def profile(self, enable=True):
+        check(self._L.kg_mocmaes_profile(self.h, int(enable)))
+
+    def profile_read(self, stage):
+        ms, n = C.c_double(), C.c_size_t()
+        check(self._L.kg_mocmaes_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
 

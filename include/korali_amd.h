@@ -779,6 +779,33 @@ typedef struct {
 } kg_vracer_config;
 
 int kg_vracer_create(const kg_vracer_config *cfg, kg_vracer_t *out);
+/* A discrete agent, Agent / Discrete / dVRACER on Reinforcement Learning /
+ * Discrete (replaces Discrete::initializeAgent, solver/agent/discrete/
+ * discrete.cpp.base:7-13; dVRACER::initializeAgent, dVRACER.cpp.base:8-57; the
+ * problem's 'Possible Actions', problem/reinforcementLearning/discrete/
+ * discrete.cpp.base:7-21): `possible_actions` = K action vectors of
+ * action_size components each (1 <= K <= 7, row-major in `actions`).  The
+ * network's output is V, K Q-values and the inverse temperature (Identity x
+ * (1 + K), Sigmoid; scale 1, shift 0); the policy is the softmax of
+ * dVRACER::runPolicy (:156-222), actions are categorical draws
+ * (Discrete::getAction, discrete.cpp.base:15-78), importance weights and
+ * gradients those of discrete.cpp.base:80-163 and dVRACER.cpp.base:83-154.
+ * cfg's policy_distribution, action bounds and initial_exploration_noise are
+ * ignored.  Every other kg_vracer_* call works on either kind of handle:
+ *   kg_vracer_run_policy       returns the 2 + K transformed outputs per row;
+ *   kg_vracer_set_action_noise forces the next step's uniforms in [0, 1), one
+ *                              per environment (n = environments);
+ *   kg_vracer_test_episodes    takes the first most probable action;
+ *   fields                     exp_policy / cur_policy are R x (K + 1) (q,
+ *                              invT); action_index (int, R),
+ *                              exp_action_probabilities and
+ *                              cur_action_probabilities (R x K),
+ *                              possible_actions (K x action_size); the running
+ *                              episodes' episode_action_index (int) and
+ *                              episode_action_probabilities (x K), environments x
+ *                              max_episode_steps slots. */
+int kg_vracer_create_discrete(const kg_vracer_config *cfg, size_t possible_actions,
+                              const double *actions /* K x action_size */, kg_vracer_t *out);
 int kg_vracer_destroy(kg_vracer_t h);
 int kg_vracer_hyperparameter_count(kg_vracer_t h, size_t *n);
 int kg_vracer_field_size(kg_vracer_t h, const char *name, size_t *elem_bytes, size_t *count);

@@ -23,7 +23,11 @@
 //   Linear / Output layers          neuralNetwork/layer/{linear,output}/*.cpp.base
 //   fAdam::processResult            solver/learner/deepSupervisor/optimizers/fAdam.cpp:64-91
 //   CartPole environment            examples/learning/reinforcement/cartpole/_model
-// The CPU restatement is oracle/vracer_ref.py (test infrastructure only).
+//   Discrete agents (dVRACER)       solver/agent/discrete/discrete.cpp.base:7-163,
+//                                   solver/agent/discrete/dVRACER/dVRACER.cpp.base:8-222
+//                                   (a discrete handle, Params::K > 0: DESIGN.md section 18)
+// The CPU restatement is oracle/vracer_ref.py (test infrastructure only;
+// tests/dvracer_ref.py restates the discrete agent on top of it).
 #include "kg_common.hpp"
 #include "../../include/korali_amd.h"
 
@@ -43,6 +47,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MAXA = 4;  // action dimensions supported by the device kernels
 constexpr int MAXO = 1 + 2 * MAXA;
+constexpr int MAXK = MAXO - 2;  // discrete handles: V, up to MAXK Q-values, the inverse temperature
+enum : int { TR_IDENTITY = 0, TR_SOFTPLUS = 1, TR_SIGMOID = 2 };  // Params::soft: an output's transformation
 constexpr int MAXB = 2048;  // mini-batch size limit (one-workgroup sort / metadata)
 constexpr int MAXENV = 64;  // reward rescaling: up to this many environment ids are staged in LDS (any count runs)
 constexpr int MAXS = 8;     // state dimensions with state rescaling
@@ -91,6 +97,7 @@ struct Params {  // launch-constant configuration
   int rr;                         // Reward / Rescaling / Enabled
   int srs;                        // State Rescaling / Enabled
   int host;                       // a host 'Environment Function' feeds the environment steps
+  int K;                          // discrete handle: the number of Possible Actions (0: continuous)
 };
 
 // ---------------------------------------------------------------- philox
@@ -158,6 +165,14 @@ __device__ inline float policy_logp(const Params &P, int i, float a, float m, fl
 }
 
 // ------------------------------------------------------------ layer kernels
+// The Output layer's transformation of one value (output.cpp.base:147-151):
+// Softplus 0.5 (x + sqrt(1 + x^2)) in double; Sigmoid 1. / (1. + exp(-x))
+// with the float exp promoted to double; each rounded to float.
+__device__ __forceinline__ float vr_out_transform(float x, int kind) {
+  if (kind == TR_SOFTPLUS) return (float)(0.5 * ((double)x + sqrt(1.0 + (double)x * (double)x)));
+  if (kind == TR_SIGMOID) return (float)(1.0 / (1.0 + (double)expf(-x)));
+  return x;
+}
 // Input layer (K = state size): H = tanh(X W1^T + b1), one thread per output.
 __global__ void k_vr_fwd_in(int M, int S, int H, const float *__restrict__ X, const float *__restrict__ W,
                             const float *__restrict__ b, float *__restrict__ Y) {
@@ -212,8 +227,7 @@ __global__ __launch_bounds__(256) void k_vr_fwd_out(int M, int H, int O, const f
     for (int o = 0; o < MAXO; o++)
       if (o == lane) x = acc[o];
     x = x + b[lane];
-    if (P.soft[lane]) x = (float)(0.5 * ((double)x + sqrt(1.0 + (double)x * (double)x)));
-    out[(long long)m * O + lane] = x * P.scale[lane] + P.shift[lane];
+    out[(long long)m * O + lane] = vr_out_transform(x, P.soft[lane]) * P.scale[lane] + P.shift[lane];
   }
 }
 
@@ -354,9 +368,11 @@ __global__ void k_vr_bwd_out(int Bn, int H, int O, const float *__restrict__ G, 
       x = x - P.shift[o];
       x = x / P.scale[o];
       g = g * P.scale[o];
-      if (P.soft[o]) {
+      if (P.soft[o] == TR_SOFTPLUS) {
         const float nnx = x - 0.25f / x;
         g = (float)((double)g * 0.5 * (1.0 + (double)nnx / sqrt((double)nnx * (double)nnx + 1.0)));
+      } else if (P.soft[o] == TR_SIGMOID) {  // output.cpp.base:208-209: g * x in float, times the double (1. - x)
+        g = (float)((double)(g * x) * (1.0 - (double)x));
       }
       dz[o] = g;
       acc += dz[o] * wo[o];
@@ -504,6 +520,11 @@ struct Replay {
   float *rsig;      // getScaledReward's sigma (1.0 until the first update)
   float *rsum;      // sum of squared rewards in the replay memory
   long long *rcnt;  // experiences in the replay memory
+  // discrete handles (policy_t of discrete agents): the action's index and the
+  // K action probabilities of the experience's and the current policy;
+  // exp_pol / cur_pol then hold the K + 1 distribution parameters (q, invT)
+  int *aidx;
+  float *exp_p, *cur_p;
 };
 __device__ inline long long phys(const State *s, long long R, long long i) {
   return (long long)((s->total - s->size + (unsigned long long)i) % (unsigned long long)R);
@@ -882,8 +903,7 @@ __global__ __launch_bounds__(256) void k_vr_fwd_fused(Params P, int M, const flo
       for (int o = 0; o < MAXO; o++)
         if (o == lane) x = acc[o];
       x = x + bo[lane];
-      if (P.soft[lane]) x = (float)(0.5 * ((double)x + sqrt(1.0 + (double)x * (double)x)));
-      out[(long long)m * O + lane] = x * P.scale[lane] + P.shift[lane];
+      out[(long long)m * O + lane] = vr_out_transform(x, P.soft[lane]) * P.scale[lane] + P.shift[lane];
     }
   }
 }
@@ -959,6 +979,117 @@ __device__ inline void kl_grad_terms(const Params &P, int i, float cm, float cs,
   ks -= curAdjUb * ccdfB;
 }
 
+// ---------------------------------------------------- discrete policy math
+// dVRACER::runPolicy (dVRACER.cpp.base:156-222) from one output row (V, K
+// Q-values, the inverse temperature): p_i = exp(invT (q_i - max q)) / sum, the
+// float sum in index order, the division as a product with 1 / sum.  Every
+// array index is a compile-time constant (loops unrolled to MAXK, i < K
+// guarded).
+__device__ __forceinline__ void vr_softmax(const float *__restrict__ row, int K, float (&q)[MAXK], float (&p)[MAXK],
+                                           float &invT) {
+  invT = row[1 + K];
+  float maxq = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++) {
+    q[i] = i < K ? row[1 + i] : 0.f;
+    if (i < K && q[i] > maxq) maxq = q[i];
+  }
+  float sum = 0.0f;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++) {
+    p[i] = 0.f;
+    if (i < K) {
+      p[i] = expf(invT * (q[i] - maxq));
+      sum += p[i];
+    }
+  }
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++)
+    if (i < K) p[i] *= inv;
+}
+// element idx of a register array (a chain of selects, no indexed access)
+__device__ __forceinline__ float vr_pick(const float (&v)[MAXK], int idx) {
+  float x = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++)
+    if (i == idx) x = v[i];
+  return x;
+}
+// Discrete::getAction (discrete.cpp.base:41-65).  Training: the categorical
+// draw from one uniform x (curSum += p_i for i < K - 1, stop at x < curSum,
+// else K - 1); testing: the first maximum of p (std::max_element).
+__device__ __forceinline__ int vr_categorical(const float (&p)[MAXK], int K, float x) {
+  float curSum = 0.0f;
+  int idx = K - 1;
+  bool open = true;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++)
+    if (open && i < K - 1) {
+      curSum += p[i];
+      if (x < curSum) idx = i, open = false;
+    }
+  return idx;
+}
+__device__ __forceinline__ int vr_argmax(const float (&p)[MAXK], int K) {
+  int idx = 0;
+  float best = p[0];
+#pragma unroll
+  for (int i = 1; i < MAXK; i++)
+    if (i < K && p[i] > best) best = p[i], idx = i;
+  return idx;
+}
+// the uniform of environment e's action at environment step `step`: one
+// philox block per (environment, step), a purpose tag of its own
+__device__ inline float philox_action_uniform(unsigned long long seed, unsigned long long step, unsigned e) {
+  const u4 r = philox4x32(u4{(unsigned)step, (unsigned)(step >> 32), e, 0x4441u}, (unsigned)seed, (unsigned)(seed >> 32));
+  return (float)(r.x >> 8) * 5.9604644775390625e-08f;  // [0, 1)
+}
+// Discrete::calculateImportanceWeight (discrete.cpp.base:80-95)
+__device__ __forceinline__ float vr_discrete_iw(float pCur, float pOld) {
+  float iw = pCur / (pOld + 0.00000001f);
+  if (iw > 1024.0f) iw = 1024.0f;
+  if (iw < -1024.0f) iw = -1024.0f;
+  return iw;
+}
+// calculateImportanceWeightGradient (discrete.cpp.base:97-132) and
+// calculateKLDivergenceGradient (:134-163) with respect to (q, invT), in the
+// written precision: the `1.` / `1.0` literals make those products double
+// before they are rounded to float, `klGrad[i] -=` rounds per term.
+__device__ __forceinline__ void vr_discrete_grads(int K, int ai, float iw, float invT, const float (&q)[MAXK],
+                                                  const float (&pc)[MAXK], const float (&po)[MAXK], float (&ig)[MAXK + 1],
+                                                  float (&kl)[MAXK + 1]) {
+  float qpSum = 0.0f;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++) {
+    ig[i] = 0.f;
+    if (i < K) {
+      if (i == ai) ig[i] = (float)((double)iw * (1.0 - (double)pc[i]) * (double)invT);
+      else ig[i] = -iw * pc[i] * invT;
+      qpSum += q[i] * pc[i];
+    }
+  }
+  ig[MAXK] = iw * (vr_pick(q, ai) - qpSum);
+#pragma unroll
+  for (int i = 0; i < MAXK; i++) {
+    float g = 0.0f;
+    if (i < K) {
+#pragma unroll
+      for (int j = 0; j < MAXK; j++)
+        if (j < K) {
+          if (i == j) g = (float)((double)g - (double)(invT * po[j]) * (1.0 - (double)pc[i]));
+          else g += invT * po[j] * pc[i];
+        }
+    }
+    kl[i] = g;
+  }
+  float gt = 0.0f;
+#pragma unroll
+  for (int j = 0; j < MAXK; j++)
+    if (j < K) gt -= po[j] * (q[j] - qpSum);
+  kl[MAXK] = gt;
+}
+
 // updateExperienceMetadata (agent.cpp.base:599-735) + the VRACER loss
 // gradient (VRACER.cpp.base:89-181) + the REF-ER schedule (agent.cpp.base:
 // 221-231), one workgroup.  Every mini-batch row's metadata lives in LDS
@@ -988,7 +1119,11 @@ __device__ __forceinline__ int u16v(unsigned short h) {
 // RR: reward rescaling enabled (every reward through getScaledReward: the
 // divisions are exact no-ops at sigma 1.0, but the retrace walk then also
 // loads each entry's environment id, so the plain form does without)
-template <bool RR>
+// DISC: a discrete handle (softmax policy over K Q-values): the importance
+// weight, the loss gradient and the stored current policy take the discrete
+// form (discrete.cpp.base:80-163, dVRACER.cpp.base:83-154); everything else is
+// shared with the continuous form
+template <bool RR, bool DISC>
 __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er, const unsigned *mb,
                                                  const float *__restrict__ out, float *__restrict__ G,
                                                  unsigned long long advance, int staged) {
@@ -1021,13 +1156,25 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
     const unsigned id = mb[b];
     const bool uniq = b == 0 || id != mb[b - 1];
     const long long p = ph(id);
-    const float a = er.act[p * P.A], om = er.exp_pol[2 * P.A * p], osd = er.exp_pol[2 * P.A * p + P.A],
-                rew = RR ? er.rew[p] / er.rsig[er.env[p]] : er.rew[p];
+    const float rew = RR ? er.rew[p] / er.rsig[er.env[p]] : er.rew[p];
     const int was = er.onp[p], term = er.term[p];
-    const float V = out[(long long)b * O], cm = out[(long long)b * O + 1], cs = out[(long long)b * O + 1 + P.A];
+    const float V = out[(long long)b * O];
     const float tvv = term == TRUNCATED ? out[(long long)(B + b) * O] : 0.0f;
-    float liw;
-    if (P.A == 1) {
+    float a = 0.f, om = 0.f, osd = 0.f, cm = 0.f, cs = 0.f;
+    if (!DISC) {
+      a = er.act[p * P.A], om = er.exp_pol[2 * P.A * p], osd = er.exp_pol[2 * P.A * p + P.A];
+      cm = out[(long long)b * O + 1], cs = out[(long long)b * O + 1 + P.A];
+    }
+    float liw = 0.f, iw;
+    if (DISC) {
+      // calculateImportanceWeight (discrete.cpp.base:80-95): the ratio of the
+      // stored action's probabilities, clamped to +-1024 (no log clamp)
+      const int K = P.K, ai = (unsigned)er.aidx[p] < (unsigned)P.K ? er.aidx[p] : 0;
+      float q[MAXK], pc[MAXK], invT;
+      vr_softmax(out + (long long)b * O, K, q, pc, invT);
+      iw = vr_discrete_iw(vr_pick(pc, ai), er.exp_p[p * K + ai]);
+      if (!isfinite(iw)) atomicOr(&st->errors, (unsigned)ERR_NONFINITE_IW);
+    } else if (P.A == 1) {
       liw = policy_logp(P, 0, a, cm, cs) - policy_logp(P, 0, a, om, osd);
     } else {  // calculateImportanceWeight's sums over the action components, in order
       const int A = P.A;
@@ -1039,11 +1186,13 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
       }
       liw = lc - lo;
     }
-    if (liw > 7.f) liw = 7.f;
-    if (liw < -7.f) liw = -7.f;
-    if (!isfinite(liw)) atomicOr(&st->errors, (unsigned)ERR_NONFINITE_IW);
+    if (!DISC) {
+      if (liw > 7.f) liw = 7.f;
+      if (liw < -7.f) liw = -7.f;
+      if (!isfinite(liw)) atomicOr(&st->errors, (unsigned)ERR_NONFINITE_IW);
+      iw = expf(liw);
+    }
     if (!isfinite(V)) atomicOr(&st->errors, (unsigned)ERR_NONFINITE_VALUE);
-    const float iw = expf(liw);
     const float tiw = iw < P.iw_trunc ? iw : P.iw_trunc;  // std::min(level, iw)
     const int onp = (iw > 1.0f / cutoff) && (iw < cutoff);
     if (uniq) {
@@ -1051,8 +1200,11 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
       if (!was && onp) delta--;
     }
     s_mb[b] = id, s_uniq[b] = uniq;
-    s_V[b] = V, s_tiw[b] = tiw, s_iw[b] = iw, s_rew[b] = rew, s_tv[b] = tvv, s_act[b] = a;
-    s_cur[2 * b] = cm, s_cur[2 * b + 1] = cs, s_old[2 * b] = om, s_old[2 * b + 1] = osd;
+    s_V[b] = V, s_tiw[b] = tiw, s_iw[b] = iw, s_rew[b] = rew, s_tv[b] = tvv;
+    if (!DISC) {
+      s_act[b] = a;
+      s_cur[2 * b] = cm, s_cur[2 * b + 1] = cs, s_old[2 * b] = om, s_old[2 * b + 1] = osd;
+    }
     s_term[b] = (unsigned char)term, s_onp[b] = (unsigned char)onp;
   }
   if (delta) atomicAdd(&s_delta, delta);
@@ -1351,17 +1503,53 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
     };
     const float V = s_V[b];
     const int term = u8v(s_term[b]);
+    const float g0 = s_ret[b] - V;
+    // Qret - V of an on-policy row (VRACER.cpp.base:118-139, dVRACER.cpp.base:110-130)
+    auto off_policy_loss = [&]() __attribute__((always_inline)) {
+      float q = s_rew[b];
+      if (term == NON_TERMINAL) q += P.gamma * s_retn[b];
+      if (term == TRUNCATED) q += P.gamma * s_tv[b];
+      return q - V;
+    };
+    unsigned bad = !isfinite(g0);
+    G[(long long)b * O] = g0;
+    if (DISC) {
+      // dVRACER::calculatePolicyGradients (dVRACER.cpp.base:83-154): the row's
+      // current policy again from the forward's output, the experience's
+      // probabilities from the replay memory
+      const int K = P.K, ai = (unsigned)er.aidx[p] < (unsigned)P.K ? er.aidx[p] : 0;
+      float q[MAXK], pc[MAXK], po[MAXK], invT, ig[MAXK + 1], kl[MAXK + 1];
+      vr_softmax(out + (long long)b * O, K, q, pc, invT);
+#pragma unroll
+      for (int i = 0; i < MAXK; i++) po[i] = i < K ? er.exp_p[p * K + i] : 0.f;
+      vr_discrete_grads(K, ai, s_iw[b], invT, q, pc, po, ig, kl);
+      const bool onp = u8v(s_onp[b]) != 0;
+      const float loss = onp ? off_policy_loss() : 0.f;
+      const bool uniq = u8v(s_uniq[b]) != 0;
+#pragma unroll
+      for (int i = 0; i <= MAXK; i++) {
+        const int o = i < MAXK ? i : K;  // the inverse temperature follows the K Q-values
+        if (i < K || i == MAXK) {
+          float g = 0.f;
+          if (onp) g = beta * loss * ig[i];
+          g += klm * kl[i];
+          bad |= !isfinite(g);
+          G[(long long)b * O + 1 + o] = g;
+          if (uniq) er.cur_pol[p * (K + 1) + o] = i < MAXK ? q[i] : invT;
+        }
+      }
+      if (uniq)
+#pragma unroll
+        for (int i = 0; i < MAXK; i++)
+          if (i < K) er.cur_p[p * K + i] = pc[i];
+    } else {
     // (means and sigmas in separate register arrays: every index a
     // compile-time constant, no indexed register access)
     float gm[MAXA], gs[MAXA];
 #pragma unroll
     for (int i = 0; i < MAXA; i++) gm[i] = gs[i] = 0.f;
-    const float g0 = s_ret[b] - V;
     if (u8v(s_onp[b])) {
-      float q = s_rew[b];
-      if (term == NON_TERMINAL) q += P.gamma * s_retn[b];
-      if (term == TRUNCATED) q += P.gamma * s_tv[b];
-      const float loss = q - V;
+      const float loss = off_policy_loss();
       // calculateImportanceWeightGradient: per component the factors, the
       // log-densities summed in component order, then the weight
       float pm[MAXA], ps[MAXA], lcs = 0.0f, los = 0.0f;
@@ -1391,8 +1579,6 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
         gm[i] += klm * km;
         gs[i] += klm * ks;
       }
-    unsigned bad = !isfinite(g0);
-    G[(long long)b * O] = g0;
 #pragma unroll
     for (int i = 0; i < MAXA; i++)
       if (i < A) {
@@ -1400,7 +1586,6 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
         G[(long long)b * O + 1 + i] = gm[i];
         G[(long long)b * O + 1 + A + i] = gs[i];
       }
-    if (bad) atomicOr(&st->errors, (unsigned)ERR_NONFINITE_GRADIENT);
     if (u8v(s_uniq[b])) {
 #pragma unroll
       for (int i = 0; i < MAXA; i++)
@@ -1409,6 +1594,10 @@ __global__ __launch_bounds__(512) void k_vr_meta(Params P, State *st, Replay er,
           comp(i, a, cm, cs, om, osd);
           er.cur_pol[p * 2 * A + i] = cm, er.cur_pol[p * 2 * A + A + i] = cs;
         }
+    }
+    }
+    if (bad) atomicOr(&st->errors, (unsigned)ERR_NONFINITE_GRADIENT);
+    if (u8v(s_uniq[b])) {
       er.v[p] = V;
       er.tv[p] = s_tv[b];
       er.iw[p] = s_iw[b];
@@ -1645,6 +1834,8 @@ struct Envs {
   int *fin_id;        // environment id of the finished episode of each rank
   float *pm, *ps;     // E x S: the state-rescaling moments the running episode was launched with
   float *hraw;        // E x S: a host environment's raw launch state (State Rescaling re-scales it)
+  int *eb_idx;        // discrete handles, E x T: the action's index; eb_p (E x T x K): the action probabilities
+  float *eb_p;        // (eb_pol then holds the K + 1 distribution parameters)
 };
 // requestNewPolicy's normalisation (reinforcementLearning.cpp.base:361-370)
 // of environment e's state component k
@@ -1699,12 +1890,23 @@ __global__ void k_vr_test_reset(Params P, const State *st, int n, int S, const u
   done[e] = 0;
   cum[e] = 0.f;
 }
+// DISC: a discrete handle takes the first maximum of the action
+// probabilities (discrete.cpp.base:64-65) and its Possible Action (pact)
+template <bool DISC>
 __global__ void k_vr_test_act(Params P, const State *st, int n, const float *__restrict__ out, double *u, double *tm,
-                              int *steps, int *done, float *cum, float *X, unsigned *errors, int *running) {
+                              int *steps, int *done, float *cum, float *X, unsigned *errors, int *running,
+                              const float *__restrict__ pact) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n || done[e]) return;
-  float act = out[(long long)e * P.O + 1];  // the mode (A = 1: the CartPole kernel)
-  if (P.clipped) {
+  float act;
+  if (DISC) {
+    float q[MAXK], p[MAXK], invT;
+    vr_softmax(out + (long long)e * P.O, P.K, q, p, invT);
+    act = pact[vr_argmax(p, P.K) * P.A];
+  } else {
+    act = out[(long long)e * P.O + 1];  // the mode (A = 1: the CartPole kernel)
+  }
+  if (!DISC && P.clipped) {
     if (act >= P.ub[0]) act = P.ub[0];
     if (act <= P.lb[0]) act = P.lb[0];
   }
@@ -1724,10 +1926,35 @@ __global__ void k_vr_test_act(Params P, const State *st, int n, const float *__r
   else atomicAdd(running, 1);
 }
 
+// A discrete handle's training action of environment e (Discrete::getAction,
+// discrete.cpp.base:15-78): the softmax policy of its output row, the
+// categorical draw from one uniform (forced, or the handle's philox stream),
+// the Possible Action of that index into act; the index, the K probabilities
+// and the K + 1 distribution parameters go to the episode buffer's slot.
+__device__ __forceinline__ void vr_discrete_act(const Params &P, const State *st, const Envs &ev, int e, long long slot,
+                                                const float *__restrict__ out, const float *__restrict__ forced,
+                                                const float *__restrict__ pact, float (&act)[MAXA]) {
+  const int K = P.K, A = P.A;
+  float q[MAXK], p[MAXK], invT;
+  vr_softmax(out + (long long)e * P.O, K, q, p, invT);
+  const float x = forced ? forced[e] : philox_action_uniform(P.seed, st->env_step, (unsigned)e);
+  const int idx = vr_categorical(p, K, x);
+#pragma unroll
+  for (int i = 0; i < MAXA; i++) act[i] = i < A ? pact[idx * A + i] : 0.f;
+  ev.eb_idx[slot] = idx;
+#pragma unroll
+  for (int i = 0; i < MAXK; i++)
+    if (i < K) ev.eb_p[slot * K + i] = p[i], ev.eb_pol[slot * (K + 1) + i] = q[i];
+  ev.eb_pol[slot * (K + 1) + K] = invT;
+}
+
 // One action of every environment (continuous.cpp.base:95-150 Normal policy:
 // action = mean + sigma N(0,1)); the experience is kept in the episode buffer.
+// DISC: a discrete handle's categorical action (vr_discrete_act); forced_noise
+// then holds one uniform per environment.
+template <bool DISC>
 __global__ void k_vr_env_act(Params P, State *st, Envs ev, const float *__restrict__ out, float *X,
-                             const float *__restrict__ forced_noise) {
+                             const float *__restrict__ forced_noise, const float *__restrict__ pact) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= P.E) return;
   const int A = P.A, S = P.S, O = P.O;
@@ -1735,6 +1962,8 @@ __global__ void k_vr_env_act(Params P, State *st, Envs ev, const float *__restri
   const long long slot = (long long)e * P.T + t;
   const float V = out[(long long)e * O];
   float act[MAXA];
+  if (DISC) vr_discrete_act(P, st, ev, e, slot, out, forced_noise, pact, act);
+  else
   for (int i = 0; i < A; i += 2) {
     float n0, n1;
     if (forced_noise) {
@@ -1746,14 +1975,15 @@ __global__ void k_vr_env_act(Params P, State *st, Envs ev, const float *__restri
     act[i] = out[(long long)e * O + 1 + i] + out[(long long)e * O + 1 + A + i] * n0;
     if (i + 1 < A) act[i + 1] = out[(long long)e * O + 2 + i] + out[(long long)e * O + 2 + A + i] * n1;
   }
-  if (P.clipped)  // continuous.cpp.base:172-183
+  if (!DISC && P.clipped)  // continuous.cpp.base:172-183
     for (int i = 0; i < A; i++) {
       if (act[i] >= P.ub[i]) act[i] = P.ub[i];
       if (act[i] <= P.lb[i]) act[i] = P.lb[i];
     }
   for (int k = 0; k < S; k++) ev.eb_st[slot * S + k] = X[(long long)e * S + k];
   for (int i = 0; i < A; i++) ev.eb_act[slot * A + i] = act[i];
-  for (int i = 0; i < 2 * A; i++) ev.eb_pol[slot * 2 * A + i] = out[(long long)e * O + 1 + i];
+  if (!DISC)
+    for (int i = 0; i < 2 * A; i++) ev.eb_pol[slot * 2 * A + i] = out[(long long)e * O + 1 + i];
   ev.eb_v[slot] = V;
   double y[4];
 #pragma unroll
@@ -1804,8 +2034,10 @@ __global__ void k_vr_host_launch(Params P, const State *st, Envs ev, float *X, c
 // the policy's action for every environment's current state (as the first
 // half of k_vr_env_act: continuous.cpp.base:95-150), the experience kept in
 // the episode buffer and the action handed to the host
+template <bool DISC>
 __global__ void k_vr_host_act(Params P, State *st, Envs ev, const float *__restrict__ out, const float *__restrict__ X,
-                              const float *__restrict__ forced_noise, float *__restrict__ actions) {
+                              const float *__restrict__ forced_noise, float *__restrict__ actions,
+                              const float *__restrict__ pact) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= P.E) return;
   const int A = P.A, S = P.S, O = P.O;
@@ -1816,6 +2048,8 @@ __global__ void k_vr_host_act(Params P, State *st, Envs ev, const float *__restr
   }
   const long long slot = (long long)e * P.T + t;
   float act[MAXA];
+  if (DISC) vr_discrete_act(P, st, ev, e, slot, out, forced_noise, pact, act);
+  else
   for (int i = 0; i < A; i += 2) {
     float n0, n1;
     if (forced_noise) {
@@ -1827,14 +2061,15 @@ __global__ void k_vr_host_act(Params P, State *st, Envs ev, const float *__restr
     act[i] = out[(long long)e * O + 1 + i] + out[(long long)e * O + 1 + A + i] * n0;
     if (i + 1 < A) act[i + 1] = out[(long long)e * O + 2 + i] + out[(long long)e * O + 2 + A + i] * n1;
   }
-  if (P.clipped)  // continuous.cpp.base:172-183
+  if (!DISC && P.clipped)  // continuous.cpp.base:172-183
     for (int i = 0; i < A; i++) {
       if (act[i] >= P.ub[i]) act[i] = P.ub[i];
       if (act[i] <= P.lb[i]) act[i] = P.lb[i];
     }
   for (int k = 0; k < S; k++) ev.eb_st[slot * S + k] = X[(long long)e * S + k];
   for (int i = 0; i < A; i++) ev.eb_act[slot * A + i] = act[i], actions[e * A + i] = act[i];
-  for (int i = 0; i < 2 * A; i++) ev.eb_pol[slot * 2 * A + i] = out[(long long)e * O + 1 + i];
+  if (!DISC)
+    for (int i = 0; i < 2 * A; i++) ev.eb_pol[slot * 2 * A + i] = out[(long long)e * O + 1 + i];
   ev.eb_v[slot] = out[(long long)e * O];
 }
 
@@ -2021,6 +2256,9 @@ __global__ void k_vr_reward_sums(Params P, State *st, Replay er, Envs ev) {
 // counts evicted off-policy entries, sets the initial retrace values (the
 // reference's last-two-entries window, see oracle/vracer_ref.py) and resets
 // the environment for its next launch.
+// DISC: a discrete handle's K + 1 distribution parameters, action index and
+// K action probabilities (the experience's and, equal at first, the current)
+template <bool DISC>
 __global__ __launch_bounds__(256) void k_vr_append(Params P, State *st, Replay er, Envs ev,
                                                    const float *__restrict__ outF, float *X,
                                                    const float *__restrict__ hnext, const int *__restrict__ hnext_id) {
@@ -2048,6 +2286,12 @@ __global__ __launch_bounds__(256) void k_vr_append(Params P, State *st, Replay e
       er.tst[p * S + q] = tk == TRUNCATED ? X[(long long)e * S + q] : 0.f;
     }
     for (int i = 0; i < A; i++) er.act[p * A + i] = ev.eb_act[slot * A + i];
+    if (DISC) {
+      const int K = P.K;
+      for (int i = 0; i < K + 1; i++) er.exp_pol[p * (K + 1) + i] = er.cur_pol[p * (K + 1) + i] = ev.eb_pol[slot * (K + 1) + i];
+      for (int i = 0; i < K; i++) er.exp_p[p * K + i] = er.cur_p[p * K + i] = ev.eb_p[slot * K + i];
+      er.aidx[p] = ev.eb_idx[slot];
+    } else
     for (int i = 0; i < 2 * A; i++) er.exp_pol[p * 2 * A + i] = er.cur_pol[p * 2 * A + i] = ev.eb_pol[slot * 2 * A + i];
     er.rew[p] = ev.eb_rew[slot];
     er.env[p] = ev.env_id[e];
@@ -2206,6 +2450,7 @@ struct kg_vracer_s {
   unsigned *mb, *forced_mb;
   float *forced_noise;
   int use_forced_noise;
+  float *pact = nullptr;  // discrete handle: the Possible Actions (K x A)
   // host environments: states / next launches' states (E x S), rewards,
   // actions (E x A), terminations and environment ids (E) staged on the device
   float *h_states = nullptr, *h_next = nullptr, *h_rew = nullptr, *h_act = nullptr;
@@ -2445,7 +2690,9 @@ int vr_update(kg_vracer_t h, const unsigned *forced, const unsigned *drawn = nul
     const int v = e ? atoi(e) : 512;
     return (v == 256 || v == 512) ? v : 512;
   }();
-  hipLaunchKernelGGL(P.rr ? k_vr_meta<true> : k_vr_meta<false>, dim3(1), dim3(metaTpb), 0, h->stream, P, h->st, h->er,
+  hipLaunchKernelGGL(P.K ? (P.rr ? k_vr_meta<true, true> : k_vr_meta<false, true>)
+                         : (P.rr ? k_vr_meta<true, false> : k_vr_meta<false, false>),
+                     dim3(1), dim3(metaTpb), 0, h->stream, P, h->st, h->er,
                      (const unsigned *)h->mb, (const float *)h->out, h->G, advance, vr_staged_walks() ? 1 : 0);
   // backward (DeepSupervisor, Direct Gradient) on the B mini-batch rows
   const size_t rs = h->rowsMax * P.H;
@@ -2525,7 +2772,14 @@ bool vr_field(kg_vracer_t h, const char *name, VrField &f) {
       {"state", h->er.st, 4, R * P.S},         {"action", h->er.act, 4, R * P.A},
       {"reward", h->er.rew, 4, R},             {"environment_id", h->er.env, 4, R},
       {"termination", h->er.term, 4, R},       {"truncated_state", h->er.tst, 4, R * P.S},
-      {"exp_policy", h->er.exp_pol, 4, R * 2 * P.A}, {"cur_policy", h->er.cur_pol, 4, R * 2 * P.A},
+      {"exp_policy", h->er.exp_pol, 4, R * (P.O - 1)}, {"cur_policy", h->er.cur_pol, 4, R * (P.O - 1)},
+      // discrete handles only (exp_policy / cur_policy are then R x (K + 1): q, invT)
+      {"action_index", h->er.aidx, 4, R},
+      {"exp_action_probabilities", h->er.exp_p, 4, R * P.K}, {"cur_action_probabilities", h->er.cur_p, 4, R * P.K},
+      {"possible_actions", h->pact, 4, (size_t)P.K * P.A},
+      // the running episodes' buffers, E x T slots (slot e T + t: environment e's step t)
+      {"episode_action_index", h->ev.eb_idx, 4, E * (size_t)P.T},
+      {"episode_action_probabilities", h->ev.eb_p, 4, E * (size_t)P.T * P.K},
       {"exp_state_value", h->er.exp_v, 4, R},  {"state_value", h->er.v, 4, R},
       {"retrace", h->er.ret, 4, R},            {"importance_weight", h->er.iw, 4, R},
       {"truncated_importance_weight", h->er.tiw, 4, R}, {"truncated_state_value", h->er.tv, 4, R},
@@ -2566,7 +2820,7 @@ bool vr_field(kg_vracer_t h, const char *name, VrField &f) {
       {"device_adam_second_moment", h->m2, 4, h->nparam},
   };
   for (auto &x : tab)
-    if (!strcmp(x.n, name)) {
+    if (x.p && !strcmp(x.n, name)) {
       f = VrField{x.p, x.elem, x.count, x.param};
       return true;
     }
@@ -2577,7 +2831,8 @@ bool vr_field(kg_vracer_t h, const char *name, VrField &f) {
 
 extern "C" {
 
-int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
+// a continuous handle (K = 0) or a discrete one (K Possible Actions of A components)
+static int vr_create(const kg_vracer_config *c, size_t K, const double *actions, kg_vracer_t *out) {
   KG_CHECK(c && out, "vracer: null argument");
   KG_CHECK(c->state_size >= 1 && c->action_size >= 1 && c->action_size <= (size_t)MAXA,
            "vracer: action size must be 1..4 and state size >= 1");
@@ -2592,12 +2847,12 @@ int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
            "vracer: Experience Replay Start Size must not exceed Maximum Size");
   KG_CHECK(c->max_episode_steps >= 1, "vracer: episodes need at least one step");
   KG_CHECK(c->off_policy_cutoff_scale >= 0.0, "Experience Replay Cutoff Scale must be larger 0.0");
-  for (size_t i = 0; i < c->action_size; i++)
+  for (size_t i = 0; !K && i < c->action_size; i++)
     KG_CHECK(c->initial_exploration_noise && c->initial_exploration_noise[i] > 0.0,
              "Provided initial noise for an action variable is not defined or negative.");
-  KG_CHECK(c->policy_distribution == 0 || c->policy_distribution == 1,
+  KG_CHECK(K || c->policy_distribution == 0 || c->policy_distribution == 1,
            "vracer: policy distribution must be 0 (Normal) or 1 (Clipped Normal)");
-  if (c->policy_distribution == 1)
+  if (!K && c->policy_distribution == 1)
     for (size_t i = 0; i < c->action_size; i++)
       KG_CHECK(c->action_lower_bounds && c->action_upper_bounds && std::isfinite(c->action_lower_bounds[i]) &&
                    std::isfinite(c->action_upper_bounds[i]),
@@ -2606,7 +2861,8 @@ int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
   auto *h = new kg_vracer_s();
   Params &P = h->P;
   P.S = (int)c->state_size, P.A = (int)c->action_size, P.H = (int)((c->hidden_size + 63) / 64 * 64), P.L = (int)c->hidden_layers;
-  P.O = 1 + 2 * P.A, P.E = (int)c->environments, P.B = (int)c->mini_batch_size, P.T = (int)c->max_episode_steps;
+  P.K = (int)K;
+  P.O = K ? (int)K + 2 : 1 + 2 * P.A, P.E = (int)c->environments, P.B = (int)c->mini_batch_size, P.T = (int)c->max_episode_steps;
   P.R = (long long)c->replay_maximum_size;
   P.env_count = (int)c->environment_count;
   P.rr = c->reward_rescaling ? 1 : 0;
@@ -2620,10 +2876,14 @@ int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
   P.anneal = (float)c->off_policy_annealing_rate, P.l2imp = (float)c->l2_regularization_importance;
   P.seed = c->seed;
   for (int o = 0; o < MAXO; o++) P.scale[o] = 1.f, P.shift[o] = 0.f, P.soft[o] = 0;
-  P.clipped = c->policy_distribution == 1 ? 1 : 0;
-  for (int i = 0; i < P.A; i++) {
+  P.clipped = !K && c->policy_distribution == 1 ? 1 : 0;
+  // dVRACER.cpp.base:35-51: Identity for V and the Q-values, Sigmoid for the
+  // inverse temperature, scale 1 and shift 0 throughout
+  if (K) P.soft[1 + K] = TR_SIGMOID;
+  for (int i = 0; i < P.A; i++) P.lb[i] = -INFINITY, P.ub[i] = INFINITY;
+  for (int i = 0; !K && i < P.A; i++) {
     P.scale[1 + P.A + i] = 2.0f * (float)c->initial_exploration_noise[i];
-    P.soft[1 + P.A + i] = 1;
+    P.soft[1 + P.A + i] = TR_SOFTPLUS;
     P.lb[i] = c->action_lower_bounds ? (float)c->action_lower_bounds[i] : -INFINITY;
     P.ub[i] = c->action_upper_bounds ? (float)c->action_upper_bounds[i] : INFINITY;
     // bounded distributions shift the means by the action shift (continuous.cpp.base:20-30, :53-54)
@@ -2698,7 +2958,8 @@ int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
   alloc(h->st, sizeof(State));
   Replay &er = h->er;
   alloc(er.st, R * P.S * 4), alloc(er.act, R * P.A * 4), alloc(er.rew, R * 4), alloc(er.tst, R * P.S * 4);
-  alloc(er.exp_pol, R * 2 * P.A * 4), alloc(er.cur_pol, R * 2 * P.A * 4), alloc(er.exp_v, R * 4), alloc(er.v, R * 4);
+  const size_t PP = (size_t)P.O - 1;  // policy parameters: 2A (means, sigmas) or K + 1 (q, invT)
+  alloc(er.exp_pol, R * PP * 4), alloc(er.cur_pol, R * PP * 4), alloc(er.exp_v, R * 4), alloc(er.v, R * 4);
   alloc(er.ret, R * 4), alloc(er.iw, R * 4), alloc(er.tiw, R * 4), alloc(er.tv, R * 4);
   alloc(er.env, R * 4), alloc(er.term, R * 4), alloc(er.onp, R * 4), alloc(er.ep_pos, R * 4), alloc(er.ep_id, R * 8);
   const size_t EC = (size_t)P.env_count;
@@ -2710,11 +2971,21 @@ int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
   Envs &ev = h->ev;
   alloc(ev.u, E * 4 * 8), alloc(ev.time, E * 8), alloc(ev.t, E * 4), alloc(ev.env_id, E * 4), alloc(ev.sample, E * 8), alloc(ev.cum, E * 4);
   alloc(ev.fin, E * 4), alloc(ev.len, E * 4), alloc(ev.off, E * 8), alloc(ev.rank, E * 4), alloc(ev.fin_env, E * 4);
-  alloc(ev.eb_st, ET * P.S * 4), alloc(ev.eb_act, ET * P.A * 4), alloc(ev.eb_pol, ET * 2 * P.A * 4);
+  alloc(ev.eb_st, ET * P.S * 4), alloc(ev.eb_act, ET * P.A * 4), alloc(ev.eb_pol, ET * PP * 4);
   alloc(ev.eb_v, ET * 4), alloc(ev.eb_rew, ET * 4), alloc(ev.rewards, E * 4);
   alloc(ev.sig2, E * 2 * 4), alloc(ev.fin_id, E * 4);
   alloc(ev.pm, (size_t)E * P.S * 4), alloc(ev.ps, (size_t)E * P.S * 4);
   if (P.host) alloc(ev.hraw, (size_t)E * P.S * 4);
+  if (K) {
+    alloc(er.aidx, R * 4), alloc(er.exp_p, R * K * 4), alloc(er.cur_p, R * K * 4);
+    alloc(ev.eb_idx, ET * 4), alloc(ev.eb_p, ET * K * 4);
+    alloc(h->pact, K * P.A * 4);
+    if (!rc) {
+      std::vector<float> pa(K * P.A);
+      for (size_t i = 0; i < pa.size(); i++) pa[i] = (float)actions[i];
+      if (hipMemcpy(h->pact, pa.data(), pa.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = 1;
+    }
+  }
   if (!rc && host_alloc((void **)&h->st_host, sizeof(State), hipHostMallocDefault) != hipSuccess) {
     kg::set_error("vracer: hipHostMalloc failed");
     rc = 1;
@@ -2738,6 +3009,16 @@ int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) {
   }
   *out = h;
   return 0;
+}
+
+int kg_vracer_create(const kg_vracer_config *c, kg_vracer_t *out) { return vr_create(c, 0, nullptr, out); }
+
+int kg_vracer_create_discrete(const kg_vracer_config *c, size_t possible_actions, const double *actions,
+                              kg_vracer_t *out) {
+  KG_CHECK(c && out && actions, "vracer: null argument");
+  KG_CHECK(possible_actions >= 1, "No possible actions have been defined for the discrete RL problem (empty set detected).");
+  KG_CHECK(possible_actions <= (size_t)MAXK, "vracer: the device policy supports up to 7 Possible Actions");
+  return vr_create(c, possible_actions, actions, out);
 }
 
 // kg_debug_cartpole_at: trajectory j advances `steps` times with
@@ -2804,7 +3085,8 @@ int kg_vracer_destroy(kg_vracer_t h) {
                   h->er.env, h->er.term, h->er.onp, h->er.ep_pos, h->er.ep_id, h->ev.u, h->ev.time, h->ev.t, h->ev.env_id,
                   h->ev.sample, h->ev.cum, h->ev.fin, h->ev.len, h->ev.off, h->ev.rank, h->ev.fin_env, h->ev.eb_st,
                   h->ev.eb_act, h->ev.eb_pol, h->ev.eb_v, h->ev.eb_rew, h->ev.rewards, h->ev.sig2, h->ev.fin_id,
-                  h->ev.pm, h->ev.ps, h->ev.hraw, h->er.rsig, h->er.rsum, h->er.rcnt};
+                  h->ev.pm, h->ev.ps, h->ev.hraw, h->er.rsig, h->er.rsum, h->er.rcnt, h->er.aidx, h->er.exp_p,
+                  h->er.cur_p, h->ev.eb_idx, h->ev.eb_p, h->pact};
   for (void *p : ptrs)
     if (p) dev_release(p);
   if (h->st_host) host_release(h->st_host);
@@ -2965,8 +3247,9 @@ int kg_vracer_test_episodes(kg_vracer_t h, const uint64_t *sample_ids, const uin
         break;
       }
       if (t % 16 == 0 && fail(hipMemsetAsync(running, 0, 4, h->stream))) break;
-      hipLaunchKernelGGL(k_vr_test_act, grid, dim3(256), 0, h->stream, h->P, (const State *)h->st, m,
-                         (const float *)h->out, u, tm, steps, done, cum, h->Xs, errs, running);
+      hipLaunchKernelGGL(h->P.K ? k_vr_test_act<true> : k_vr_test_act<false>, grid, dim3(256), 0, h->stream, h->P,
+                         (const State *)h->st, m, (const float *)h->out, u, tm, steps, done, cum, h->Xs, errs, running,
+                         (const float *)h->pact);
       if (t % 16 == 15) {  // every 16 steps: stop once every episode has ended
         int r = 0;
         if (fail(hipMemcpyAsync(&r, running, 4, hipMemcpyDeviceToHost, h->stream)) ||
@@ -2998,7 +3281,8 @@ int kg_vracer_set_action_noise(kg_vracer_t h, const float *noise, size_t n) {
     h->use_forced_noise = 0;
     return 0;
   }
-  KG_CHECK(n == (size_t)h->P.E * h->P.A, "vracer: action noise must hold Concurrent Environments x action size values");
+  if (h->P.K) KG_CHECK(n == (size_t)h->P.E, "vracer: a discrete agent's forced uniforms must hold Concurrent Environments values");
+  else KG_CHECK(n == (size_t)h->P.E * h->P.A, "vracer: action noise must hold Concurrent Environments x action size values");
   KG_HIP(hipMemcpyAsync(h->forced_noise, noise, n * 4, hipMemcpyHostToDevice, h->stream));
   h->use_forced_noise = 1;
   return 0;
@@ -3011,15 +3295,16 @@ int kg_vracer_environment_step(kg_vracer_t h, size_t *new_experiences) {
   {
   VrStage te(h, "environment_step");
   if (vr_forward(h, h->X, P.E, h->out)) return 1;
-  hipLaunchKernelGGL(k_vr_env_act, dim3(vr_blocks(P.E, 256)), dim3(256), 0, h->stream, P, h->st, h->ev,
-                     (const float *)h->out, h->X, h->use_forced_noise ? (const float *)h->forced_noise : nullptr);
+  hipLaunchKernelGGL(P.K ? k_vr_env_act<true> : k_vr_env_act<false>, dim3(vr_blocks(P.E, 256)), dim3(256), 0, h->stream,
+                     P, h->st, h->ev, (const float *)h->out, h->X,
+                     h->use_forced_noise ? (const float *)h->forced_noise : nullptr, (const float *)h->pact);
   h->use_forced_noise = 0;
   if (vr_forward(h, h->X, P.E, h->outF)) return 1;  // V of truncated states (agent.cpp.base:530-545)
   hipLaunchKernelGGL(k_vr_scan, dim3(1), dim3(1024), 0, h->stream, P, h->st, h->ev);
   hipLaunchKernelGGL(k_vr_evict, dim3(1), dim3(256), 0, h->stream, P, h->st, h->er);
   if (P.rr) hipLaunchKernelGGL(k_vr_reward_sums, dim3(1), dim3(64), 0, h->stream, P, h->st, h->er, h->ev);
-  hipLaunchKernelGGL(k_vr_append, dim3(P.E), dim3(256), 0, h->stream, P, h->st, h->er, h->ev, (const float *)h->outF,
-                     h->X, (const float *)nullptr, (const int *)nullptr);
+  hipLaunchKernelGGL(P.K ? k_vr_append<true> : k_vr_append<false>, dim3(P.E), dim3(256), 0, h->stream, P, h->st, h->er,
+                     h->ev, (const float *)h->outF, h->X, (const float *)nullptr, (const int *)nullptr);
   KG_HIP(hipGetLastError());
   }
   if (vr_read_state(h)) return 1;
@@ -3051,9 +3336,10 @@ int kg_vracer_host_act(kg_vracer_t h, float *actions) {
   {
     VrStage te(h, "environment_step");
     if (vr_forward(h, h->X, P.E, h->out)) return 1;
-    hipLaunchKernelGGL(k_vr_host_act, dim3(vr_blocks(P.E, 256)), dim3(256), 0, h->stream, P, h->st, h->ev,
-                       (const float *)h->out, (const float *)h->X,
-                       h->use_forced_noise ? (const float *)h->forced_noise : nullptr, h->h_act);
+    hipLaunchKernelGGL(P.K ? k_vr_host_act<true> : k_vr_host_act<false>, dim3(vr_blocks(P.E, 256)), dim3(256), 0,
+                       h->stream, P, h->st, h->ev, (const float *)h->out, (const float *)h->X,
+                       h->use_forced_noise ? (const float *)h->forced_noise : nullptr, h->h_act,
+                       (const float *)h->pact);
     KG_HIP(hipGetLastError());
   }
   h->use_forced_noise = 0;
@@ -3086,8 +3372,8 @@ int kg_vracer_host_feed(kg_vracer_t h, const float *rewards, const float *states
     hipLaunchKernelGGL(k_vr_scan, dim3(1), dim3(1024), 0, h->stream, P, h->st, h->ev);
     hipLaunchKernelGGL(k_vr_evict, dim3(1), dim3(256), 0, h->stream, P, h->st, h->er);
     if (P.rr) hipLaunchKernelGGL(k_vr_reward_sums, dim3(1), dim3(64), 0, h->stream, P, h->st, h->er, h->ev);
-    hipLaunchKernelGGL(k_vr_append, dim3(P.E), dim3(256), 0, h->stream, P, h->st, h->er, h->ev,
-                       (const float *)h->outF, h->X, (const float *)h->h_next, (const int *)h->h_ids);
+    hipLaunchKernelGGL(P.K ? k_vr_append<true> : k_vr_append<false>, dim3(P.E), dim3(256), 0, h->stream, P, h->st,
+                       h->er, h->ev, (const float *)h->outF, h->X, (const float *)h->h_next, (const int *)h->h_ids);
     KG_HIP(hipGetLastError());
   }
   if (vr_read_state(h)) return 1;

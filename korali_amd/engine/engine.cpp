@@ -2372,6 +2372,7 @@ const KeyList RL_KEYS = {"Type", "Environment Function", "Environment Kernel", "
                          "Actions Between Policy Updates", "Agents Per Environment", "Policies Per Environment",
                          "Testing Frequency", "Policy Testing Episodes", "Custom Settings", "Max Episode Steps",
                          "State Vector Size", "Action Vector Size", "State Vector Indexes", "Action Vector Indexes"};
+const KeyList DISCRETE_RL_KEYS = {"Possible Actions"};  // problem/reinforcementLearning/discrete/discrete.config
 
 }  // namespace
 
@@ -2427,6 +2428,54 @@ Json vracerPolicyDescription(Json &js) {
   Json &hl = sv["Neural Network"]["Hidden Layers"];
   for (size_t l = 0; 2 * l < hl.size(); l++) sizes.push_back(uint(hl[2 * l], "Output Channels", 0));
   sizes.push_back(1 + 2 * A);
+  unsigned long long count = 0;
+  for (size_t l = 0; l + 1 < sizes.size(); l++) count += sizes[l] * sizes[l + 1] + sizes[l + 1];
+  out["Layer Sizes"] = sizes;
+  out["Hyperparameter Count"] = count;
+  return out;
+}
+
+// The discrete agents' description (Discrete::initializeAgent,
+// solver/agent/discrete/discrete.cpp.base:7-13; dVRACER::initializeAgent,
+// dVRACER.cpp.base:21-51; the problem's checks, problem/reinforcementLearning/
+// discrete/discrete.cpp.base:15-20): K + 1 policy parameters (K Q-values,
+// the inverse temperature), scale 1, shift 0, Identity x K then Sigmoid.
+Json dvracerPolicyDescription(Json &js) {
+  Json &sv = js["Solver"];
+  Json &pb = js["Problem"];
+  std::vector<unsigned long long> sIdx, aIdx;
+  for (size_t i = 0; i < js["Variables"].size(); i++) {
+    const std::string t = canon(str(js["Variables"][i], "Type", "State"));
+    if (t == "state") sIdx.push_back(i);
+    else if (t == "action") aIdx.push_back(i);
+  }
+  const size_t A = aIdx.size();
+  const size_t K = pb.contains("Possible Actions") && pb["Possible Actions"].is_array() ? pb["Possible Actions"].size() : 0;
+  if (K == 0) fail("No possible actions have been defined for the discrete RL problem (empty set detected).\n");
+  for (size_t i = 0; i < K; i++) {
+    Json &a = pb["Possible Actions"][i];
+    const size_t n = a.is_array() ? a.size() : 0;
+    if (n != A)
+      fail("For possible action %lu, incorrect vector size provided. Expected: %lu, Provided: %lu.\n", (unsigned long)i,
+           (unsigned long)A, (unsigned long)n);
+  }
+  std::vector<float> scaling(K + 1, 1.0f), shifting(K + 1, 0.0f);
+  std::vector<std::string> masks(K + 1, "Identity");
+  masks[K] = "Sigmoid";
+  Json out;
+  out["Problem"]["State Vector Size"] = (unsigned long long)sIdx.size();
+  out["Problem"]["Action Vector Size"] = (unsigned long long)A;
+  out["Problem"]["State Vector Indexes"] = sIdx;
+  out["Problem"]["Action Vector Indexes"] = aIdx;
+  out["Solver"]["Policy"]["Parameter Count"] = (unsigned long long)(K + 1);
+  out["Solver"]["Policy"]["Parameter Scaling"] = scaling;
+  out["Solver"]["Policy"]["Parameter Shifting"] = shifting;
+  out["Solver"]["Policy"]["Parameter Transformation Masks"] = masks;
+  // network: state -> [Linear (H), Tanh] x L -> Linear (value, Q-values, inverse temperature)
+  std::vector<unsigned long long> sizes{(unsigned long long)sIdx.size()};
+  Json &hl = sv["Neural Network"]["Hidden Layers"];
+  for (size_t l = 0; 2 * l < hl.size(); l++) sizes.push_back(uint(hl[2 * l], "Output Channels", 0));
+  sizes.push_back(2 + K);
   unsigned long long count = 0;
   for (size_t l = 0; l + 1 < sizes.size(); l++) count += sizes[l] * sizes[l + 1] + sizes[l + 1];
   out["Layer Sizes"] = sizes;
@@ -2568,7 +2617,14 @@ int readEnvTermination(EnvCoroutine &c) {
        t.c_str());
 }
 
-struct VracerModule : SolverModule {
+// The agent on the device, continuous (VRACER) or discrete (dVRACER: the
+// problem's 'Possible Actions', a softmax policy over Q-values); the two
+// solver modules below differ in this flag only
+struct AgentModule : SolverModule {
+  const bool discrete;
+  const char *const solverName;  // "VRACER" / "dVRACER"
+  std::vector<double> possibleActions;  // discrete: K x nAction
+  size_t nPossible = 0;
   size_t envIds = 1;  // Problem / Environment Count
   kg_vracer_t h = nullptr;
   double maxGenerations = 1e10;
@@ -2594,21 +2650,35 @@ struct VracerModule : SolverModule {
   std::vector<std::unique_ptr<EnvCoroutine>> envs;
   unsigned long long nextSampleId = 0, nextLaunchId = 0;  // agent.cpp.base:186; reinforcementLearning.cpp.base:71
 
-  ~VracerModule() override {
+  ~AgentModule() override {
     envs.clear();  // (the functions unwind before the agent goes)
     if (h) kg_vracer_destroy(h);
   }
 
-  VracerModule(Json &js, Seeder &seeds, bool resume) {
+  AgentModule(Json &js, Seeder &seeds, bool resume, bool discrete_)
+      : discrete(discrete_), solverName(discrete_ ? "dVRACER" : "VRACER") {
     Json &sv = js["Solver"];
     Json &pb = js["Problem"];
     solverJs = &sv;
     const std::string pt = canon(str(pb, "Type", ""));
-    if (pt != "reinforcementlearning/continuous")
-      fail("Solver VRACER requires a problem of type 'Reinforcement Learning / Continuous' (is '%s').",
-           pb["Type"].getString().c_str());
-    rejectUnrecognised(sv, "VRACER", {SOLVER_KEYS, AGENT_KEYS}, {SOLVER_TERMINATION, AGENT_TERMINATION});
-    rejectUnrecognised(pb, "Continuous", {RL_KEYS}, {});
+    if (pt != (discrete ? "reinforcementlearning/discrete" : "reinforcementlearning/continuous"))
+      fail("Solver %s requires a problem of type 'Reinforcement Learning / %s' (is '%s').", solverName,
+           discrete ? "Discrete" : "Continuous", pb["Type"].getString().c_str());
+    if (discrete) {
+      // the agent keys without continuous.config's 'Policy' / 'Distribution'
+      // ('Policy' itself holds the description a result file carries); the
+      // problem's 'Possible Actions'
+      if (sv.contains("Policy") && sv["Policy"].contains("Distribution")) {
+        Json left = Json::object();
+        left["Policy"]["Distribution"] = sv["Policy"]["Distribution"];
+        fail(" + Unrecognized settings for Korali module: %s: \n%s\n", "dVRACER", left.dump(2).c_str());
+      }
+      rejectUnrecognised(sv, "dVRACER", {SOLVER_KEYS, AGENT_KEYS}, {SOLVER_TERMINATION, AGENT_TERMINATION});
+      rejectUnrecognised(pb, "Discrete", {RL_KEYS, DISCRETE_RL_KEYS}, {});
+    } else {
+      rejectUnrecognised(sv, "VRACER", {SOLVER_KEYS, AGENT_KEYS}, {SOLVER_TERMINATION, AGENT_TERMINATION});
+      rejectUnrecognised(pb, "Continuous", {RL_KEYS}, {});
+    }
     const std::string mode = canon(str(sv, "Mode", "Training"));
     if (mode != "training" && mode != "testing") fail("'Mode' must be 'Training' or 'Testing'.");
     testing = mode == "testing";
@@ -2651,8 +2721,8 @@ struct VracerModule : SolverModule {
       if (t == "state") nState++;
       else if (t == "action") {
         nAction++;
-        const double noise = num(v, "Initial Exploration Noise", -1.0);
-        if (noise <= 0.0)
+        const double noise = num(v, "Initial Exploration Noise", -1.0);  // (dVRACER.config: present, unused)
+        if (!discrete && noise <= 0.0)
           fail("Provided initial noise (%f) for action variable %zu is not defined or negative.\n", noise, i);
         const double lb = num(v, "Lower Bound", -INFINITY), ub = num(v, "Upper Bound", INFINITY);
         if (ub - lb <= 0.0) fail("Upper (%f) and Lower Bound (%f) of action variable %zu invalid.\n", ub, lb, i);
@@ -2665,7 +2735,15 @@ struct VracerModule : SolverModule {
       fail("The CartPole environment kernel has 4 state variables and 1 action variable (%zu / %zu given).", nState,
            nAction);
     if (nAction > 4) fail("The device policy supports up to 4 action variables (%zu given).", nAction);
-    const std::string dist = canon(str(sv["Policy"], "Distribution", "Normal"));
+    if (discrete) {
+      // problem/reinforcementLearning/discrete/discrete.cpp.base:15-20 (dvracerPolicyDescription raises them)
+      description = dvracerPolicyDescription(js);
+      nPossible = pb["Possible Actions"].size();
+      if (nPossible > 7) fail("The device policy supports up to 7 'Possible Actions' (%zu given).", nPossible);
+      for (size_t i = 0; i < nPossible; i++)
+        for (size_t j = 0; j < nAction; j++) possibleActions.push_back(pb["Possible Actions"][i][j].getDouble());
+    }
+    const std::string dist = discrete ? std::string("normal") : canon(str(sv["Policy"], "Distribution", "Normal"));
     if (dist != "normal" && dist != "clippednormal")
       fail("Policy Distribution '%s' is not supported by the device path (Normal, Clipped Normal).",
            sv["Policy"]["Distribution"].getString().c_str());
@@ -2717,9 +2795,9 @@ struct VracerModule : SolverModule {
     serialize = flag(er, "Serialize", true);
     c.replay_maximum_size = maxSize, c.replay_start_size = startSize;
     c.max_episode_steps = (size_t)maxSteps;
-    c.experiences_between_policy_updates = mandatory(sv, "Experiences Between Policy Updates", "VRACER");
+    c.experiences_between_policy_updates = mandatory(sv, "Experiences Between Policy Updates", solverName);
     c.discount_factor = num(sv, "Discount Factor", 0.995);
-    c.learning_rate = mandatory(sv, "Learning Rate", "VRACER");
+    c.learning_rate = mandatory(sv, "Learning Rate", solverName);
     c.importance_weight_truncation_level = num(sv, "Importance Weight Truncation Level", 1.0);
     c.off_policy_cutoff_scale = num(op, "Cutoff Scale", 4.0);
     c.off_policy_target = num(op, "Target", 0.1);
@@ -2741,7 +2819,8 @@ struct VracerModule : SolverModule {
     maxEpisodes = uint(tc, "Max Episodes", 0);
     maxExperiences = uint(tc, "Max Experiences", 0);
     maxPolicyUpdates = uint(tc, "Max Policy Updates", 0);
-    check(kg_vracer_create(&c, &h));
+    if (discrete) check(kg_vracer_create_discrete(&c, nPossible, possibleActions.data(), &h));
+    else check(kg_vracer_create(&c, &h));
     // initial hyperparameters (linear.cpp.base:28-49): Xavier-scaled U(-1, 1)
     // weights, zero biases, output layer Weight Scaling 0.001 (VRACER.cpp.base:38).
     // The uniform stream is this build's (std::mt19937 seeded from the
@@ -2750,10 +2829,10 @@ struct VracerModule : SolverModule {
     check(kg_vracer_hyperparameter_count(h, &n));
     std::vector<size_t> sizes{nState};
     for (size_t l = 0; l < L; l++) sizes.push_back(H);
-    sizes.push_back(1 + 2 * nAction);
+    sizes.push_back(outputs());
     std::vector<float> theta = vracerInitialHyperparameters(sizes, (unsigned)seeds.counter++);
-    if (theta.size() != n) fail("VRACER: hyperparameter count mismatch (%zu vs the device's %zu).", theta.size(), n);
-    description = vracerPolicyDescription(js);
+    if (theta.size() != n) fail("%s: hyperparameter count mismatch (%zu vs the device's %zu).", solverName, theta.size(), n);
+    if (!discrete) description = vracerPolicyDescription(js);
     if (sv["Training"].contains("Current Policy") && sv["Training"]["Current Policy"].contains("Policy") &&
         sv["Training"]["Current Policy"]["Policy"].size() == n) {
       auto v = flatten(sv["Training"]["Current Policy"]["Policy"]);
@@ -2809,6 +2888,39 @@ struct VracerModule : SolverModule {
         check(kg_vracer_set_field(h, "reward_rescaling_sigma", sg.data(), envIds * sizeof(float)));
       }
     }
+  }
+
+  // the network's outputs per row: V and the policy parameters
+  size_t outputs() const { return discrete ? 2 + nPossible : 1 + 2 * nAction; }
+
+  // a testing agent's action from one output row: the policy's mode
+  // (generateTestingAction, continuous.cpp.base:219-260), or the Possible
+  // Action of the first largest probability (discrete.cpp.base:64-65, the
+  // softmax of dVRACER.cpp.base:174-211 in float)
+  std::vector<float> testingAction(const std::vector<float> &out) const {
+    const size_t A = nAction;
+    if (discrete) {
+      const size_t K = nPossible;
+      const float invT = out[1 + K];
+      float maxq = -INFINITY;
+      for (size_t i = 0; i < K; i++) maxq = std::max(maxq, out[1 + i]);
+      std::vector<float> p(K);
+      float sum = 0.0f;
+      for (size_t i = 0; i < K; i++) sum += p[i] = std::exp(invT * (out[1 + i] - maxq));
+      const float inv = 1.0f / sum;
+      for (size_t i = 0; i < K; i++) p[i] *= inv;
+      const size_t idx = (size_t)(std::max_element(p.begin(), p.end()) - p.begin());
+      std::vector<float> a(A);
+      for (size_t i = 0; i < A; i++) a[i] = (float)possibleActions[idx * A + i];
+      return a;
+    }
+    std::vector<float> a(out.begin() + 1, out.begin() + 1 + A);
+    if (clipped)
+      for (size_t i = 0; i < A; i++) {
+        if (a[i] >= (float)actUbs[i]) a[i] = (float)actUbs[i];
+        if (a[i] <= (float)actLbs[i]) a[i] = (float)actLbs[i];
+      }
+    return a;
   }
 
   double scalar(const char *name) {
@@ -2888,7 +3000,7 @@ struct VracerModule : SolverModule {
   // sample: the policy's mode (generateTestingAction, continuous.cpp.base:
   // 219-260) on the state rescaled with the agent's moments (:365-376)
   void hostTestingEpisodes() {
-    const size_t S = nState, A = nAction, O = 1 + 2 * A, SM = std::min<size_t>(S, 8);
+    const size_t S = nState, O = outputs(), SM = std::min<size_t>(S, 8);
     std::vector<float> mean(S, 0.f), sdev(S, 1.f), st(S), out(O);
     check(kg_vracer_get_field(h, "state_rescaling_means", mean.data(), SM * sizeof(float)));
     check(kg_vracer_get_field(h, "state_rescaling_sigmas", sdev.data(), SM * sizeof(float)));
@@ -2901,13 +3013,7 @@ struct VracerModule : SolverModule {
       for (;;) {
         for (size_t k = 0; k < S; k++) st[k] = (st[k] - mean[k]) / sdev[k];
         check(kg_vracer_run_policy(h, st.data(), 1, out.data()));
-        std::vector<float> a(out.begin() + 1, out.begin() + 1 + A);
-        if (clipped)
-          for (size_t i = 0; i < A; i++) {
-            if (a[i] >= (float)actUbs[i]) a[i] = (float)actUbs[i];
-            if (a[i] <= (float)actLbs[i]) a[i] = (float)actLbs[i];
-          }
-        c.s["Action"] = a;
+        c.s["Action"] = testingAction(out);
         c.resume();
         readEnvState(c.s, S, st.data());
         total += readEnvReward(c.s);
@@ -3019,8 +3125,10 @@ struct VracerModule : SolverModule {
       sv["State Rescaling"]["Sigmas"] = std::vector<double>(ss.begin(), ss.end());
     }
     Json &ds = description["Solver"];
-    sv["Action Shifts"] = ds["Action Shifts"];
-    sv["Action Scales"] = ds["Action Scales"];
+    if (!discrete) {
+      sv["Action Shifts"] = ds["Action Shifts"];
+      sv["Action Scales"] = ds["Action Scales"];
+    }
     for (const char *k : {"Parameter Count", "Parameter Scaling", "Parameter Shifting", "Parameter Transformation Masks"})
       sv["Policy"][k] = ds["Policy"][k];
   }
@@ -3059,7 +3167,15 @@ struct VracerModule : SolverModule {
     log.log(2, " + Best Reward:                 %f\n", bestReward);
   }
 
-  std::string type() const override { return "Agent/Continuous/VRACER"; }
+  std::string type() const override { return discrete ? "Agent/Discrete/dVRACER" : "Agent/Continuous/VRACER"; }
+};
+struct VracerModule : AgentModule {
+  VracerModule(Json &js, Seeder &seeds, bool resume) : AgentModule(js, seeds, resume, false) {}
+};
+// Agent / Discrete / dVRACER (discrete.cpp.base, dVRACER.cpp.base) on
+// Reinforcement Learning / Discrete
+struct DvracerModule : AgentModule {
+  DvracerModule(Json &js, Seeder &seeds, bool resume) : AgentModule(js, seeds, resume, true) {}
 };
 
 // KORALI_AMD_RUN_PHASES=1: the wall time of each phase of a run on stderr
@@ -3169,9 +3285,14 @@ void runExperiment(Experiment &e, Conduit &conduit) {
       fail("Agent/Continuous/VRACER does not shard across ranks: run one experiment per GPU with the Sequential "
            "conduit (independent replicas).");
     st.solver.reset(new VracerModule(js, seeds, resume));
+  } else if (stype == "agent/discrete/dvracer" || stype == "dvracer") {
+    if (dist)
+      fail("Agent/Discrete/dVRACER does not shard across ranks: run one experiment per GPU with the Sequential "
+           "conduit (independent replicas).");
+    st.solver.reset(new DvracerModule(js, seeds, resume));
   } else {
-    fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Optimizer/MOCMAES, Sampler/TMCMC "
-         "and Agent/Continuous/VRACER).",
+    fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Optimizer/MOCMAES, Sampler/TMCMC, "
+         "Agent/Continuous/VRACER and Agent/Discrete/dVRACER).",
          sv["Type"].getString().c_str());
   }
   clk.mark("setup");

@@ -182,6 +182,10 @@ Json bayesianEvaluate(Json &experiment, const std::vector<double> &x);
 // count.  Written into VRACER result files; pinned by the reference's
 // tests/python/rlview/abf2d_vracer* files.
 Json vracerPolicyDescription(Json &experiment);
+// The same for Agent / Discrete / dVRACER: K + 1 policy parameters (the
+// Q-values of the K 'Possible Actions', the inverse temperature); raises the
+// Discrete problem's two 'Possible Actions' errors.
+Json dvracerPolicyDescription(Json &experiment);
 // the last run's generation completion marks: marks[0] = the loop's first
 // termination check, marks[i] = when generation i's check returned (seconds
 // from the start of the loop; timing hook, not part of the experiment state)

@@ -150,7 +150,7 @@ EXPORTED = [
     "kg_debug_cartpole_at",
     "kg_debug_host_tridiag", "kg_debug_host_chase",
     # VRACER (korali_amd/vracer.py binds their argument types)
-    "kg_vracer_create", "kg_vracer_destroy", "kg_vracer_hyperparameter_count", "kg_vracer_field_size",
+    "kg_vracer_create", "kg_vracer_create_discrete", "kg_vracer_destroy", "kg_vracer_hyperparameter_count", "kg_vracer_field_size",
     "kg_vracer_get_field", "kg_vracer_set_field", "kg_vracer_get_scalar", "kg_vracer_set_scalar",
     "kg_vracer_run_policy", "kg_vracer_set_action_noise", "kg_vracer_environment_step", "kg_vracer_train_policy",
     "kg_vracer_train_policy_minibatch", "kg_vracer_training_step", "kg_vracer_test_episodes", "kg_vracer_rescale_states", "kg_vracer_synchronize", "kg_vracer_stream",

@@ -16,7 +16,7 @@ from .native import KoraliDeviceError, check, lib
 _DTYPES = {
     "environment_id": np.int32, "termination": np.int32, "on_policy": np.int32, "episode_pos": np.int32,
     "env_steps": np.int32, "env_ids": np.int32, "finished_env": np.int32, "mini_batch": np.uint32,
-    "episode_id": np.int64, "env_u": np.float64, "env_sample_ids": np.uint64, "reward_rescaling_count": np.int64, "meta_phase_ticks": np.uint64,
+    "action_index": np.int32, "episode_action_index": np.int32, "episode_id": np.int64, "env_u": np.float64, "env_sample_ids": np.uint64, "reward_rescaling_count": np.int64, "meta_phase_ticks": np.uint64,
 }
 
 
@@ -47,6 +47,7 @@ def _lib():
         vp, sz, cp = C.c_void_p, C.c_size_t, C.c_char_p
         fp = C.POINTER(C.c_float)
         L.kg_vracer_create.argtypes = [C.POINTER(_VracerCfg), C.POINTER(vp)]
+        L.kg_vracer_create_discrete.argtypes = [C.POINTER(_VracerCfg), sz, C.POINTER(C.c_double), C.POINTER(vp)]
         for f in ("kg_vracer_destroy", "kg_vracer_synchronize"):
             getattr(L, f).argtypes = [vp]
         L.kg_vracer_hyperparameter_count.argtypes = [vp, C.POINTER(sz)]
@@ -84,7 +85,12 @@ def _fptr(a):
 
 class VracerDevice:
     """One VRACER agent on one GPU.  Keyword names follow the reference's JSON
-    keys (agent.config / VRACER.config), e.g. `mini_batch_size` = "Mini Batch"/"Size"."""
+    keys (agent.config / VRACER.config), e.g. `mini_batch_size` = "Mini Batch"/"Size".
+
+    `possible_actions=[[...], ...]` (K vectors of `action_size` components, K <= 7)
+    creates a discrete agent (Agent / Discrete / dVRACER): the outputs per row are
+    V, K Q-values and the inverse temperature, `environment_step(noise=...)` takes
+    one uniform in [0, 1) per environment."""
 
     def __init__(self, state_size=4, action_size=1, hidden_size=256, hidden_layers=2, environments=4096,
                  environment_count=3, mini_batch_size=256, replay_maximum_size=262144, replay_start_size=131072,
@@ -93,10 +99,20 @@ class VracerDevice:
                  off_policy_target=0.1, off_policy_annealing_rate=0.0, off_policy_refer_beta=0.3,
                  l2_regularization_enabled=False, l2_regularization_importance=1e-4, initial_exploration_noise=1.0,
                  seed=0, device=0, hyperparameters=None, policy_distribution="Normal", action_lower_bound=-np.inf,
-                 action_upper_bound=np.inf, reward_rescaling=False, state_rescaling=False, host_environment=False):
+                 action_upper_bound=np.inf, reward_rescaling=False, state_rescaling=False, host_environment=False,
+                 possible_actions=None):
         L = _lib()
         self.S, self.A, self.H, self.L = state_size, action_size, hidden_size, hidden_layers
         self.E, self.B, self.O = environments, mini_batch_size, 1 + 2 * action_size
+        self.K = 0
+        if possible_actions is not None:
+            pa = np.ascontiguousarray(possible_actions, np.float64)
+            if pa.size == 0:
+                raise KoraliDeviceError("No possible actions have been defined for the discrete RL problem "
+                                        "(empty set detected).")
+            if pa.ndim != 2 or pa.shape[1] != action_size:
+                raise KoraliDeviceError(f"possible_actions must be K vectors of {action_size} components")
+            self.K, self.O, self._pa = pa.shape[0], 2 + pa.shape[0], pa
         noise = np.ascontiguousarray(np.broadcast_to(np.asarray(initial_exploration_noise, np.float64),
                                                      (action_size,)))
         self._noise = noise
@@ -115,7 +131,11 @@ class VracerDevice:
                          self._ub.ctypes.data_as(C.POINTER(C.c_double)), int(bool(reward_rescaling)),
                          int(bool(state_rescaling)), int(bool(host_environment)))
         h = C.c_void_p()
-        check(L.kg_vracer_create(C.byref(cfg), C.byref(h)))
+        if self.K:
+            check(L.kg_vracer_create_discrete(C.byref(cfg), self.K, self._pa.ctypes.data_as(C.POINTER(C.c_double)),
+                                              C.byref(h)))
+        else:
+            check(L.kg_vracer_create(C.byref(cfg), C.byref(h)))
         self._h = h
         n = C.c_size_t()
         check(L.kg_vracer_hyperparameter_count(h, C.byref(n)))

@@ -883,6 +883,121 @@ int kg_vracer_stream(kg_vracer_t h, void **stream);
 int kg_vracer_profile(kg_vracer_t h, int enable);
 int kg_vracer_profile_read(kg_vracer_t h, const char *stage, double *ms_total, size_t *count);
 
+/* -------------------------------------------------------------- Nested */
+/* Sampler/Nested (nested sampling, resampling methods Box and Ellipse),
+ * Nested.cpp.base; restated in tests/nested_ref.py:
+ *   kg_nested_create            Nested::setInitialConfiguration   Nested.cpp.base:59-149
+ *   kg_nested_first_generation  Nested::runFirstGeneration        Nested.cpp.base:206-251
+ *   kg_nested_generation        Nested::runGeneration             Nested.cpp.base:151-204
+ *                               (the `while (accepted == false)` loop of :167-201) and the
+ *                               Termination Criteria of Nested.config:63-83
+ *   kg_nested_prepare           updateBounds :253-273 (updateBox :493-504, updateEllipse
+ *                               :623-632, :685-878, mahalanobisDistance :880-897),
+ *                               generateCandidates :402-443, priorTransform :275-279,
+ *                               Bayesian::evaluateLogPrior bayesian.cpp.base:24-32,
+ *                               logPriorWeight :366-376; generation 1: the draws of :208-210
+ *   kg_nested_get_candidates / kg_nested_set_evaluations
+ *                               KORALI_START / WAITANY / GET of :172-197 and :216-241
+ *   kg_nested_eval_builtin      Bayesian::evaluateLogPosterior    bayesian.cpp.base:56-77
+ *   kg_nested_process           Nested::processGeneration         Nested.cpp.base:297-364
+ *                               (sortLiveSamplesAscending :506-516, updateDeadSamples :518-530,
+ *                               updateEffectiveSamples :981-987, setBoundsVolume :378-392,
+ *                               safeLogPlus auxiliar/math.hpp:165-171); generation 1: :243-250
+ *   kg_nested_finalize          Nested::finalize :1017-1027 (consumeLiveSamples :532-578,
+ *                               generatePosterior :580-612, safeLogMinus math.hpp:180-196)
+ *   kg_nested_permutation       the std::shuffle of :584-586
+ * The live set, the bounds, the candidates and both generators live on the
+ * device; the evidence recurrences, the dead database and the posterior are
+ * host code of this library (libm exp / log / log1p, as the reference).
+ * Ties of logPriorWeight + logLikelihood rank the lower live index first.
+ * Limits: 1 <= N <= 64, Ellipse N >= 3, L >= 2, B >= 1; "Multi Ellipse" is
+ * not built. */
+typedef struct kg_nested_s *kg_nested_t;
+
+enum kg_nested_method { KG_NESTED_BOX = 0, KG_NESTED_ELLIPSE = 1, KG_NESTED_MULTI_ELLIPSE = 2 /* rejected */ };
+/* bits of kg_nested_generation's terminated_by (Nested.config:63-83) */
+enum kg_nested_termination {
+  KG_NESTED_MIN_LOG_EVIDENCE_DELTA = 1,
+  KG_NESTED_MAX_EFFECTIVE_SAMPLE_SIZE = 2,
+  KG_NESTED_MAX_LOG_LIKELIHOOD = 4
+};
+
+typedef struct {
+  size_t variable_count;            /* N */
+  size_t number_live_points;        /* "Number Live Points" (L) */
+  size_t batch_size;                /* "Batch Size" (B) */
+  int add_live_points;              /* "Add Live Points" */
+  int resampling_method;            /* enum kg_nested_method */
+  size_t proposal_update_frequency; /* "Proposal Update Frequency" */
+  double ellipsoidal_scaling;       /* "Ellipsoidal Scaling" */
+  double min_log_evidence_delta;    /* Termination Criteria */
+  double max_effective_sample_size;
+  double max_log_likelihood;
+  /* priors as in kg_tmcmc_cfg: the two parameters of each variable's
+   * distribution and its enum kg_prior_kind (NULL: every prior Uniform) */
+  const double *prior_min;
+  const double *prior_max;
+  const int *prior_kind;
+  /* the variables' "Lower Bound" / "Upper Bound": the unit cube's image for
+   * a non-Uniform prior (Nested.cpp.base:77-90); not read for Uniform ones,
+   * may be NULL when every prior is Uniform */
+  const double *lower_bound;
+  const double *upper_bound;
+  uint64_t uniform_seed, normal_seed;
+  uint64_t shuffle_seed;            /* _shuffleSeed (:61) */
+  int likelihood;                   /* enum kg_likelihood, or -1: set by the caller */
+  size_t window_tries;              /* tries the first window of a draw holds (0: default) */
+  size_t max_windows;               /* windows one draw may use before it fails (0: 4096) */
+  int device;
+} kg_nested_cfg;
+
+int kg_nested_create(const kg_nested_cfg *cfg, kg_nested_t *out);
+int kg_nested_destroy(kg_nested_t h);
+int kg_nested_first_generation(kg_nested_t h);
+/* one generation > 1 with the builtin likelihood; *terminated_by (may be
+ * NULL) receives the criteria that hold afterwards */
+int kg_nested_generation(kg_nested_t h, size_t generation, int *terminated_by);
+/* the same in stages, for likelihoods evaluated by the caller: prepare, read
+ * the transformed candidates (L rows at generation 1, B after), set their
+ * log-likelihoods (-inf allowed, NaN an error), process; repeat the three
+ * at the same generation until *accepted is non-zero (generation 1 always
+ * accepts) */
+int kg_nested_prepare(kg_nested_t h, size_t generation);
+int kg_nested_get_candidates(kg_nested_t h, double *X, size_t ld);
+int kg_nested_set_evaluations(kg_nested_t h, const double *loglik);
+int kg_nested_eval_builtin(kg_nested_t h);
+int kg_nested_process(kg_nested_t h, size_t generation, int *accepted, int *terminated_by);
+int kg_nested_finalize(kg_nested_t h);
+/* named state, keys as in Nested.config's Internal Settings ("Live Samples",
+ * "Live LogLikelihoods", "Live LogPriors", "Live LogPrior Weights", "Live
+ * Samples Rank", "Candidates", "Candidate LogLikelihoods", "Candidate
+ * LogPriors", "Candidate LogPrior Weights", "Box Lower Bound", "Box Upper
+ * Bound", "Ellipse Axes", "Dead Samples", "Dead LogLikelihoods", "Dead
+ * LogPriors", "Dead LogPrior Weights", "Dead LogWeights", "Prior Lower
+ * Bound", "Prior Width" and every scalar: "LStar", "LogEvidence", ...), the
+ * rest of ellipse_t as "Ellipse Mean", "Covariance Matrix", "Ellipse Inverse
+ * Covariance", "Ellipse Determinant", "Ellipse Volume", the results
+ * "Posterior Samples Database", "Posterior Samples LogPrior Database" and
+ * "Posterior Samples LogLikelihood Database", and "Model Evaluation Count";
+ * counts and ranks travel as doubles.  Setting "Dead Samples" sets the
+ * database's row count; the other dead fields follow with the same rows. */
+int kg_nested_field_size(kg_nested_t h, const char *name, size_t *n);
+int kg_nested_get_field(kg_nested_t h, const char *name, double *out, size_t n);
+int kg_nested_set_field(kg_nested_t h, const char *name, const double *in, size_t n);
+/* 5000-byte GSL states.  which: 0 Normal, 1 Uniform generator. */
+int kg_nested_get_rng(kg_nested_t h, int which, void *state5000);
+int kg_nested_set_rng(kg_nested_t h, int which, const void *state5000);
+/* Diagnostics only (any pointer may be NULL): windows and tries the last
+ * candidate draw used, and the current window size in tries. */
+int kg_nested_diagnostics(kg_nested_t h, size_t *last_windows, size_t *last_tries, size_t *window_tries);
+/* stage timing as kg_cmaes_profile; stages "bounds", "draw", "evaluate", "select" */
+int kg_nested_profile(kg_nested_t h, int enable);
+int kg_nested_profile_read(kg_nested_t h, const char *stage, double *ms_total, size_t *count);
+int kg_nested_synchronize(kg_nested_t h); /* waits and reports device-side errors */
+/* out[0..n) = iota(n) after std::shuffle(..., std::default_random_engine(seed))
+ * (Nested.cpp.base:584-586).  Host only. */
+int kg_nested_permutation(uint64_t seed, size_t n, size_t *out);
+
 #ifdef __cplusplus
 }
 #endif

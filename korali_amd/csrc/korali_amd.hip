@@ -10,3 +10,4 @@
 #include "kg_hier.hip"
 #include "kg_tmcmc.hip"
 #include "kg_vracer.hip"
+#include "kg_nested.hip"

@@ -1834,6 +1834,414 @@ struct MocmaesModule : SolverModule {
   std::string type() const override { return "Optimizer/MOCMAES"; }
 };
 
+// ------------------------------------------- Bayesian problems, shared
+// What the samplers read of a Bayesian problem (TMCMC and Nested): every
+// variable's prior, and how the likelihood is evaluated.
+struct PriorSpec {
+  std::vector<double> pmin, pmax;  // the two parameters of each variable's distribution
+  std::vector<int> pdist, pkind;   // its index in 'Distributions', its enum kg_prior_kind
+};
+
+// Bayesian::initialize + evaluateLogPrior (bayesian.cpp.base:6-32)
+PriorSpec readPriors(Json &js, const std::vector<VariableSpec> &vars, bool uniformOnly, const char *solver) {
+  const size_t N = vars.size();
+  Json &ds = js["Distributions"];
+  const size_t ndist = ds.size();
+  PriorSpec p;
+  p.pmin.resize(N);
+  p.pmax.resize(N);
+  p.pdist.resize(N);
+  p.pkind.assign(N, 0);
+  for (size_t i = 0; i < N; i++) {
+    Json &v = js["Variables"][i];
+    if (!v.contains("Prior Distribution")) fail("Variable '%s' has no 'Prior Distribution'.", vars[i].name.c_str());
+    const std::string pn = v["Prior Distribution"].getString();
+    int k = -1;
+    for (size_t d = 0; d < ndist; d++)
+      if (ds[d].contains("Name") && ds[d]["Name"].getString() == pn) k = (int)d;
+    if (k < 0) fail("Did not find a distribution named '%s'.", pn.c_str());
+    const std::string dt = canon(ds[k]["Type"].getString());
+    if (dt != "univariate/uniform" && uniformOnly)
+      fail("Only 'Univariate/Uniform' priors allowed (is %s).\n", ds[k]["Type"].getString().c_str());
+    if (dt == "univariate/uniform") {
+      p.pmin[i] = mandatory(ds[k], "Minimum", "Distributions");
+      p.pmax[i] = mandatory(ds[k], "Maximum", "Distributions");
+    } else {
+      // the two parameters of each supported distribution and its
+      // updateDistribution check (exponential.cpp.base has none: a Mean <= 0
+      // is accepted, its log-density is then NaN / infinite as the reference's)
+      const PriorKind *kd = nullptr;
+      for (const PriorKind &q : PRIOR_KINDS)
+        if (dt == q.type) kd = &q;
+      if (!kd)
+        fail("The device %s path supports 'Univariate/Uniform', 'Univariate/Normal', 'Univariate/Exponential', "
+             "'Univariate/Laplace', 'Univariate/Cauchy' and 'Univariate/LogNormal' priors (distribution '%s').",
+             solver, pn.c_str());
+      p.pkind[i] = kd->kind;
+      p.pmin[i] = mandatory(ds[k], kd->a, "Distributions");
+      p.pmax[i] = mandatory(ds[k], kd->b, "Distributions");
+      if (kd->what && !(p.pmax[i] > 0.0)) fail("Incorrect %s distribution: %f.\n", kd->what, p.pmax[i]);
+    }
+    p.pdist[i] = k;
+  }
+  return p;
+}
+
+struct LikelihoodSpec {
+  bool builtin = false;  // the gaussian kernel on the device
+  size_t fn = 0;         // the host function otherwise
+  std::vector<double> referenceData;
+  std::string likelihoodModel;
+};
+
+LikelihoodSpec readLikelihood(Json &lpb, bool reference) {
+  LikelihoodSpec l;
+  if (reference) {
+    // Reference::initialize (reference.cpp.base:17-23) + the model checks
+    // of evaluateLoglikelihood (:25-44)
+    if (!lpb.contains("Computational Model") || !lpb["Computational Model"].is_integer())
+      fail("Problem 'Bayesian/Reference' requires a 'Computational Model' function.");
+    l.fn = lpb["Computational Model"].getUInt();
+    if (lpb.contains("Reference Data") && lpb["Reference Data"].is_array()) l.referenceData = flatten(lpb["Reference Data"]);
+    l.likelihoodModel = str(lpb, "Likelihood Model", "");
+    if (l.referenceData.empty())
+      fail("Bayesian (%s) problems require defining reference data.\n", l.likelihoodModel.c_str());
+    if (!isReferenceLikelihoodModel(l.likelihoodModel))
+      fail("Bayesian problem (%s) not recognized.\n", l.likelihoodModel.c_str());
+  } else if (lpb.contains("Likelihood Kernel")) {
+    if (canon(lpb["Likelihood Kernel"].getString()) != "gaussian")
+      fail("Unknown 'Likelihood Kernel' '%s'.", lpb["Likelihood Kernel"].getString().c_str());
+    l.builtin = true;
+  } else {
+    if (!lpb.contains("Likelihood Model")) fail("Problem 'Bayesian/Custom' requires a 'Likelihood Model'.");
+    l.fn = lpb["Likelihood Model"].getUInt();
+  }
+  return l;
+}
+
+// -------------------------------------------------------------- Nested
+// Nested.config
+const KeyList NESTED_KEYS = {
+    // Configuration Settings
+    "Number Live Points", "Batch Size", "Add Live Points", "Resampling Method", "Proposal Update Frequency",
+    "Ellipsoidal Scaling",
+    // Internal Settings
+    "Uniform Generator", "Normal Generator", "Multivariate Generator", "Accepted Samples", "Generated Samples",
+    "LogEvidence", "LogEvidence Var", "LogVolume", "Bound LogVolume", "Last Accepted", "Next Update", "Information",
+    "LStar", "LStarOld", "LogWeight", "Expected LogShrinkage", "Max Evaluation", "Remaining Log Evidence",
+    "Log Evidence Difference", "Effective Sample Size", "Sum Log Weights", "Sum Square Log Weights",
+    "Prior Lower Bound", "Prior Width", "Candidates", "Candidate LogLikelihoods", "Candidate LogPriors",
+    "Candidate LogPrior Weights", "Live Samples", "Live LogLikelihoods", "Live LogPriors", "Live LogPrior Weights",
+    "Live Samples Rank", "Number Dead Samples", "Dead Samples", "Dead LogLikelihoods", "Dead LogPriors",
+    "Dead LogPrior Weights", "Dead LogWeights", "Covariance Matrix", "Log Domain Size", "Domain Mean",
+    "Box Lower Bound", "Box Upper Bound", "Ellipse Axes",
+    // state this build writes (the rest of the reference's ellipse_t)
+    "Ellipse Mean", "Ellipse Inverse Covariance", "Ellipse Determinant", "Ellipse Volume", "Shuffle Seed"};
+const KeyList NESTED_TERMINATION = {"Min Log Evidence Delta", "Max Effective Sample Size", "Max Log Likelihood"};
+
+const char *NESTED_SCALARS[] = {"LogEvidence", "LogEvidence Var", "LogVolume", "Bound LogVolume", "Information",
+                                "LStar", "LStarOld", "LogWeight", "Expected LogShrinkage", "Max Evaluation",
+                                "Remaining Log Evidence", "Log Evidence Difference", "Effective Sample Size",
+                                "Sum Log Weights", "Sum Square Log Weights"};
+const char *NESTED_COUNTS[] = {"Accepted Samples", "Generated Samples", "Last Accepted", "Next Update",
+                               "Number Dead Samples", "Model Evaluation Count"};
+const char *NESTED_VECTORS[] = {"Candidate LogLikelihoods", "Candidate LogPriors", "Candidate LogPrior Weights",
+                                "Live LogLikelihoods", "Live LogPriors", "Live LogPrior Weights",
+                                "Dead LogLikelihoods", "Dead LogPriors", "Dead LogPrior Weights", "Dead LogWeights"};
+// 'Dead Samples' first: it sets the database's row count for the other dead fields
+const char *NESTED_MATRICES[] = {"Dead Samples", "Candidates", "Live Samples"};
+const char *NESTED_BOX[] = {"Box Lower Bound", "Box Upper Bound"};
+const char *NESTED_ELLIPSE_VECTORS[] = {"Ellipse Mean", "Ellipse Determinant", "Ellipse Volume"};
+const char *NESTED_ELLIPSE_MATRICES[] = {"Ellipse Axes", "Covariance Matrix", "Ellipse Inverse Covariance"};
+
+struct NestedModule : SolverModule {
+  kg_nested_t h = nullptr;
+  size_t N = 0, L = 0, B = 0;
+  bool ellipse = true, reference = false, addLivePoints = true;
+  LikelihoodSpec lik;
+  std::string method;
+  double maxGenerations, maxModelEvaluations, minLogEvidenceDelta, maxEffectiveSampleSize, maxLogLikelihood;
+  double scaling;
+  size_t frequency = 0;
+  unsigned long long shuffleSeed = 0;
+
+  ~NestedModule() override {
+    if (h) kg_nested_destroy(h);
+  }
+
+  NestedModule(Json &js, Seeder &seeds, bool resume, Collective *dist) {
+    Json &sv = js["Solver"];
+    Json &pb = js["Problem"];
+    const std::string pt = canon(str(pb, "Type", ""));
+    if (pt != "bayesian/custom" && pt != "bayesian/reference")
+      fail("The device Nested path supports problems of type 'Bayesian/Custom' and 'Bayesian/Reference' (is '%s').",
+           pb["Type"].getString().c_str());
+    if (dist)
+      fail("Sampler/Nested does not shard across ranks: the Distributed conduit is not provided for this solver "
+           "(Sequential or Concurrent).");
+    rejectUnrecognised(sv, "Nested", {SOLVER_KEYS, NESTED_KEYS}, {SOLVER_TERMINATION, NESTED_TERMINATION});
+    rejectProblemUnrecognised(pb, pt);
+    reference = pt == "bayesian/reference";
+    const std::vector<VariableSpec> vars = readVariables(js);
+    N = vars.size();
+    // Nested.config:318-335
+    L = uint(sv, "Number Live Points", 1500);
+    B = uint(sv, "Batch Size", 1);
+    addLivePoints = flag(sv, "Add Live Points", true);
+    method = str(sv, "Resampling Method", "Ellipse");
+    const long long freq = (long long)num(sv, "Proposal Update Frequency", 1500);
+    scaling = num(sv, "Ellipsoidal Scaling", 1.0);
+    Json &tc = sv["Termination Criteria"];
+    maxGenerations = num(tc, "Max Generations", 1e10);
+    maxModelEvaluations = num(tc, "Max Model Evaluations", 1e9);
+    minLogEvidenceDelta = num(tc, "Min Log Evidence Delta", 0.01);
+    maxEffectiveSampleSize = num(tc, "Max Effective Sample Size", 10e6);
+    maxLogLikelihood = num(tc, "Max Log Likelihood", 10e6);
+    // setInitialConfiguration (Nested.cpp.base:61-93), in its order
+    if (minLogEvidenceDelta < 0.) fail("Min Log Evidence Delta must be larger equal 0.0 (is %lf).\n", minLogEvidenceDelta);
+    if (method != "Box" && method != "Ellipse" && method != "Multi Ellipse")
+      fail("Only accepted Resampling Method are 'Box', 'Ellipse' and 'Multi Ellipse' (is %s).\n", method.c_str());
+    if (freq <= 0) fail("Proposal Update Frequency must be larger 0");
+    frequency = (size_t)freq;
+    const PriorSpec ps = readPriors(js, vars, false, "Nested");
+    std::vector<double> lb(N), ub(N);
+    for (size_t d = 0; d < N; d++) {
+      lb[d] = vars[d].lb;
+      ub[d] = vars[d].ub;
+      if (ps.pkind[d] == KG_PRIOR_UNIFORM) continue;
+      const std::string t = js["Distributions"][(size_t)ps.pdist[d]]["Type"].getString();
+      if (!std::isfinite(lb[d]))
+        fail("Prior of variable %s is not 'Univariate/Uniform' (is %s) AND lower bound not set (invalid "
+             "configuration).\n", vars[d].name.c_str(), t.c_str());
+      if (!std::isfinite(ub[d]))
+        fail("Prior of variable %s is not 'Univariate/Uniform' (is %s) AND upper bound not set (invalid "
+             "configuration).\n", vars[d].name.c_str(), t.c_str());
+    }
+    if ((method == "Ellipse" || method == "Multi Ellipse") && N < 3)
+      fail("Resampling Method 'Ellipse' and 'Multi Ellipse' only suitable for problems of dim larger 2 (use Resampling "
+           "Method 'Box').");
+    if (method == "Multi Ellipse")
+      fail("Resampling Method 'Multi Ellipse' is not provided on the device path (use 'Box' or 'Ellipse').");
+    ellipse = method == "Ellipse";
+    lik = readLikelihood(pb, reference);
+    // generators in Nested.config Internal Settings order: Uniform, Normal, Multivariate
+    Json &gu = sv["Uniform Generator"], &gn = sv["Normal Generator"], &gm = sv["Multivariate Generator"];
+    gu["Type"] = "Univariate/Uniform";
+    gu["Minimum"] = 0.0;
+    gu["Maximum"] = 1.0;
+    gn["Type"] = "Univariate/Normal";
+    gn["Mean"] = 0.0;
+    gn["Standard Deviation"] = 1.0;
+    gm["Type"] = "Multivariate/Normal";
+    kg_nested_cfg c{};
+    c.variable_count = N;
+    c.number_live_points = L;
+    c.batch_size = B;
+    c.add_live_points = addLivePoints ? 1 : 0;
+    c.resampling_method = ellipse ? KG_NESTED_ELLIPSE : KG_NESTED_BOX;
+    c.proposal_update_frequency = frequency;
+    c.ellipsoidal_scaling = scaling;
+    c.min_log_evidence_delta = minLogEvidenceDelta;
+    c.max_effective_sample_size = maxEffectiveSampleSize;
+    c.max_log_likelihood = maxLogLikelihood;
+    c.prior_min = ps.pmin.data();
+    c.prior_max = ps.pmax.data();
+    c.prior_kind = ps.pkind.data();
+    c.lower_bound = lb.data();
+    c.upper_bound = ub.data();
+    c.uniform_seed = seeds.assign(gu);
+    c.normal_seed = seeds.assign(gn);
+    (void)seeds.assign(gm);  // seeded and saved, never drawn from
+    // _shuffleSeed = _k->_randomSeed++ (:61), after the generators' seeds
+    if (!resume || !sv.contains("Shuffle Seed")) sv["Shuffle Seed"] = seeds.counter++;
+    shuffleSeed = sv["Shuffle Seed"].getUInt();
+    c.shuffle_seed = shuffleSeed;
+    c.likelihood = lik.builtin ? KG_LIK_GAUSSIAN : -1;
+    c.device = solverDevice(js, nullptr);
+    check(kg_nested_create(&c, &h));
+    try {  // (the destructor of a partly constructed object does not run)
+      unsigned char st[5000];
+      if (seeds.range(gu, st)) check(kg_nested_set_rng(h, 1, st));
+      if (ellipse && seeds.range(gn, st)) check(kg_nested_set_rng(h, 0, st));
+      if (resume) restore(sv);
+    } catch (...) {
+      kg_nested_destroy(h);
+      h = nullptr;
+      throw;
+    }
+  }
+
+  void setField(Json &sv, const char *k) {
+    if (!sv.contains(k) || !sv[k].is_array()) return;
+    std::vector<double> v = flatten(sv[k]);
+    if (kg_nested_set_field(h, k, v.data(), v.size()) != 0)
+      fail("Resuming Sampler/Nested: saved field '%s' has %zu values: %s", k, v.size(), kg_last_error());
+  }
+
+  // Nested::setConfiguration of a saved state (loadState + resume)
+  void restore(Json &sv) {
+    for (const char *k : NESTED_MATRICES) setField(sv, k);
+    for (const char *k : NESTED_VECTORS) setField(sv, k);
+    setField(sv, "Live Samples Rank");
+    if (ellipse) {
+      for (const char *k : NESTED_ELLIPSE_MATRICES) setField(sv, k);
+      for (const char *k : NESTED_ELLIPSE_VECTORS)
+        if (sv.contains(k) && sv[k].is_number()) {
+          const double v = sv[k].getDouble();
+          check(kg_nested_set_field(h, k, &v, 1));
+        } else {
+          setField(sv, k);
+        }
+    } else {
+      for (const char *k : NESTED_BOX) setField(sv, k);
+    }
+    for (const char *k : NESTED_SCALARS)
+      if (sv.contains(k) && sv[k].is_number()) {
+        const double v = sv[k].getDouble();
+        check(kg_nested_set_field(h, k, &v, 1));
+      }
+    for (const char *k : NESTED_COUNTS)
+      if (sv.contains(k) && sv[k].is_number()) {
+        const double v = sv[k].getDouble();
+        check(kg_nested_set_field(h, k, &v, 1));
+      }
+  }
+
+  std::vector<double> vector(const char *k) {
+    size_t n = 0;
+    check(kg_nested_field_size(h, k, &n));
+    std::vector<double> v(n);
+    check(kg_nested_get_field(h, k, v.data(), n));
+    return v;
+  }
+
+  // KORALI_START / WAITANY of :172-197 and :216-241 through the conduit:
+  // Bayesian::evaluateLogPosterior evaluates the model only behind a finite prior
+  void evaluateHost(size_t gen, size_t rows, const char *priors) {
+    std::vector<double> X(rows * N), LL(rows, -INFINITY);
+    check(kg_nested_get_candidates(h, X.data(), N));
+    const std::vector<double> LP = vector(priors);
+    std::vector<size_t> todo;
+    for (size_t i = 0; i < rows; i++)
+      if (!(std::isinf(LP[i]) && LP[i] < 0)) todo.push_back(i);
+    Function &f = getFunction(lik.fn);
+    conduit->evaluateBatch(todo.size(), [&](size_t k) {
+      const size_t i = todo[k];
+      Sample s;
+      s["Module"] = "Problem";
+      s["Operation"] = "Evaluate";
+      s["Sample Id"] = (unsigned long long)i;
+      s["Current Generation"] = (unsigned long long)gen;
+      s["Parameters"] = std::vector<double>(X.begin() + i * N, X.begin() + (i + 1) * N);
+      f(s);
+      if (reference) s["logLikelihood"] = referenceLoglikelihood(lik.likelihoodModel, lik.referenceData, s);
+      if (!s.contains("logLikelihood")) fail("The likelihood model did not assign 'logLikelihood' for sample %zu.", i);
+      LL[i] = s["logLikelihood"].getDouble();
+      if (std::isnan(LL[i])) fail("Sample %zu returned NaN logLikelihood evaluation.\n", i);
+    });
+    check(kg_nested_set_evaluations(h, LL.data()));
+  }
+
+  void runGeneration(size_t gen) override {
+    if (lik.builtin) {
+      check(kg_nested_generation(h, gen, nullptr));
+      return;
+    }
+    if (gen == 1) {
+      check(kg_nested_prepare(h, 1));
+      evaluateHost(gen, L, "Live LogPriors");
+      check(kg_nested_process(h, 1, nullptr, nullptr));
+      return;
+    }
+    for (int accepted = 0; !accepted;) {  // :167-201
+      check(kg_nested_prepare(h, gen));
+      evaluateHost(gen, B, "Candidate LogPriors");
+      check(kg_nested_process(h, gen, &accepted, nullptr));
+    }
+  }
+
+  // criteria evaluated before generation `gen`: _k->_currentGeneration is gen - 1
+  void checkTermination(size_t gen, std::vector<std::string> &met) override {
+    check(kg_nested_synchronize(h));
+    if (gen > maxGenerations) met.push_back("Max Generations");
+    if (maxModelEvaluations <= vector("Model Evaluation Count")[0]) met.push_back("Max Model Evaluations");
+    // Nested.config:63-83
+    if (gen - 1 > 1 && vector("Log Evidence Difference")[0] <= minLogEvidenceDelta) met.push_back("Min Log Evidence Delta");
+    if (maxEffectiveSampleSize <= vector("Effective Sample Size")[0]) met.push_back("Max Effective Sample Size");
+    if (maxLogLikelihood <= vector("LStar")[0]) met.push_back("Max Log Likelihood");
+  }
+
+  void getConfiguration(Json &sv) override {
+    for (const char *k : NESTED_SCALARS) sv[k] = vector(k)[0];
+    for (const char *k : NESTED_COUNTS) sv[k] = (unsigned long long)vector(k)[0];
+    for (const char *k : NESTED_VECTORS) sv[k] = vector(k);
+    for (const char *k : NESTED_MATRICES) {
+      const std::vector<double> v = vector(k);
+      sv[k] = matrixJson(v, v.size() / N, N);
+    }
+    {
+      Json a = Json::array();
+      for (double x : vector("Live Samples Rank")) a.push_back((unsigned long long)x);
+      sv["Live Samples Rank"] = a;
+    }
+    sv["Prior Lower Bound"] = vector("Prior Lower Bound");
+    sv["Prior Width"] = vector("Prior Width");
+    if (ellipse) {
+      for (const char *k : NESTED_ELLIPSE_MATRICES) {
+        const std::vector<double> v = vector(k);
+        sv[k] = matrixJson(v, N, N);
+      }
+      sv["Ellipse Mean"] = vector("Ellipse Mean");
+      sv["Ellipse Determinant"] = vector("Ellipse Determinant")[0];
+      sv["Ellipse Volume"] = vector("Ellipse Volume")[0];
+    } else {
+      for (const char *k : NESTED_BOX) sv[k] = vector(k);
+    }
+    sv["Domain Mean"] = std::vector<double>(N, 0.0);  // resized, never written (:133)
+    sv["Variable Count"] = (unsigned long long)N;
+    sv["Number Live Points"] = (unsigned long long)L;
+    sv["Batch Size"] = (unsigned long long)B;
+    sv["Add Live Points"] = addLivePoints;
+    sv["Resampling Method"] = method;
+    sv["Proposal Update Frequency"] = (unsigned long long)frequency;
+    sv["Ellipsoidal Scaling"] = scaling;
+    sv["Shuffle Seed"] = shuffleSeed;
+    unsigned char st[5000];
+    check(kg_nested_get_rng(h, 1, st));
+    sv["Uniform Generator"]["Range"] = hexState(st);
+    check(kg_nested_get_rng(h, 0, st));
+    sv["Normal Generator"]["Range"] = hexState(st);
+  }
+
+  // Nested::finalize (:1017-1027)
+  void finalize(Json &js) override {
+    if (vector("Generated Samples")[0] <= (double)L) return;  // :1019: nothing after the first generation
+    check(kg_nested_finalize(h));
+    const std::vector<double> x = vector("Posterior Samples Database");
+    js["Results"]["Posterior Samples Database"] = matrixJson(x, x.size() / N, N);
+    js["Results"]["Posterior Samples LogPrior Database"] = vector("Posterior Samples LogPrior Database");
+    js["Results"]["Posterior Samples LogLikelihood Database"] = vector("Posterior Samples LogLikelihood Database");
+  }
+
+  // printGenerationAfter (:1002-1015)
+  void printAfter(const Logger &log) override {
+    const double le = vector("LogEvidence")[0], var = vector("LogEvidence Var")[0];
+    const double acc = vector("Accepted Samples")[0], gen = vector("Generated Samples")[0];
+    log.log(1, "Log Evidence: %.4f (+- %.4f)\n", le, std::sqrt(var));
+    log.log(1, "Sampling Efficiency: %.2f%%\n", 100.0 * acc / (gen - (double)L));
+    log.log(3, "Last Accepted: %zu\n", (size_t)vector("Last Accepted")[0]);
+    log.log(3, "Effective Sample Size: %.2f\n", vector("Effective Sample Size")[0]);
+    const double lv = vector("LogVolume")[0];
+    log.log(3, "Log Volume (shrinkage): %.2f/%.2f (%.2f%%)\n", lv, vector("Bound LogVolume")[0],
+            100. * (1. - std::exp(lv)));
+    log.log(2, "lStar: %.2f (max llk evaluation %.2f)\n", vector("LStar")[0], vector("Max Evaluation")[0]);
+    log.log(1, "Remaining Log Evidence: %.2f (dlogz: %.3f)\n", vector("Remaining Log Evidence")[0],
+            vector("Log Evidence Difference")[0]);
+  }
+
+  std::string type() const override { return "Sampler/Nested"; }
+};
+
 // --------------------------------------------------------------- TMCMC
 const char *TMCMC_VECTORS[] = {"Chain Leaders LogLikelihoods", "Chain Leaders LogPriors", "Chain Lengths",
                                "Mean Theta", "Covariance Matrix", "Chain Candidates LogLikelihoods",
@@ -1925,63 +2333,18 @@ struct TmcmcModule : SolverModule {
 
     // priors: each variable's Univariate/Uniform or Univariate/Normal
     // distribution (Bayesian::evaluateLogPrior, bayesian.cpp.base:24-32)
-    Json &ds = js["Distributions"];
-    ndist = ds.size();
-    std::vector<double> pmin(N), pmax(N);
-    std::vector<int> pdist(N), pkind(N, 0);
-    for (size_t i = 0; i < N; i++) {
-      Json &v = js["Variables"][i];
-      if (!v.contains("Prior Distribution")) fail("Variable '%s' has no 'Prior Distribution'.", vars[i].name.c_str());
-      const std::string pn = v["Prior Distribution"].getString();
-      int k = -1;
-      for (size_t d = 0; d < ndist; d++)
-        if (ds[d].contains("Name") && ds[d]["Name"].getString() == pn) k = (int)d;
-      if (k < 0) fail("Did not find a distribution named '%s'.", pn.c_str());
-      const std::string dt = canon(ds[k]["Type"].getString());
-      if (dt != "univariate/uniform" && mtmcmc)
-        fail("Only 'Univariate/Uniform' priors allowed (is %s).\n", ds[k]["Type"].getString().c_str());
-      if (dt == "univariate/uniform") {
-        pmin[i] = mandatory(ds[k], "Minimum", "Distributions");
-        pmax[i] = mandatory(ds[k], "Maximum", "Distributions");
-      } else {
-        // the two parameters of each supported distribution and its
-        // updateDistribution check (exponential.cpp.base has none: a Mean <= 0
-        // is accepted, its log-density is then NaN / infinite as the reference's)
-        const PriorKind *kd = nullptr;
-        for (const PriorKind &q : PRIOR_KINDS)
-          if (dt == q.type) kd = &q;
-        if (!kd)
-          fail("The device TMCMC path supports 'Univariate/Uniform', 'Univariate/Normal', 'Univariate/Exponential', "
-               "'Univariate/Laplace', 'Univariate/Cauchy' and 'Univariate/LogNormal' priors (distribution '%s').",
-               pn.c_str());
-        pkind[i] = kd->kind;
-        pmin[i] = mandatory(ds[k], kd->a, "Distributions");
-        pmax[i] = mandatory(ds[k], kd->b, "Distributions");
-        if (kd->what && !(pmax[i] > 0.0)) fail("Incorrect %s distribution: %f.\n", kd->what, pmax[i]);
-      }
-      pdist[i] = k;
-    }
+    ndist = js["Distributions"].size();
+    PriorSpec ps = readPriors(js, vars, mtmcmc, "TMCMC");
+    std::vector<double> &pmin = ps.pmin, &pmax = ps.pmax;
+    std::vector<int> &pdist = ps.pdist, &pkind = ps.pkind;
     if (hierarchical) {
       builtin = true;  // no host callback, no 'Computational Model'
-    } else if (reference) {
-      // Reference::initialize (reference.cpp.base:17-23) + the model checks
-      // of evaluateLoglikelihood (:25-44)
-      if (!lpb.contains("Computational Model") || !lpb["Computational Model"].is_integer())
-        fail("Problem 'Bayesian/Reference' requires a 'Computational Model' function.");
-      fn = lpb["Computational Model"].getUInt();
-      if (lpb.contains("Reference Data") && lpb["Reference Data"].is_array()) referenceData = flatten(lpb["Reference Data"]);
-      likelihoodModel = str(lpb, "Likelihood Model", "");
-      if (referenceData.empty())
-        fail("Bayesian (%s) problems require defining reference data.\n", likelihoodModel.c_str());
-      if (!isReferenceLikelihoodModel(likelihoodModel))
-        fail("Bayesian problem (%s) not recognized.\n", likelihoodModel.c_str());
-    } else if (lpb.contains("Likelihood Kernel")) {
-      if (canon(lpb["Likelihood Kernel"].getString()) != "gaussian")
-        fail("Unknown 'Likelihood Kernel' '%s'.", lpb["Likelihood Kernel"].getString().c_str());
-      builtin = true;
     } else {
-      if (!lpb.contains("Likelihood Model")) fail("Problem 'Bayesian/Custom' requires a 'Likelihood Model'.");
-      fn = lpb["Likelihood Model"].getUInt();
+      LikelihoodSpec ls = readLikelihood(lpb, reference);
+      builtin = ls.builtin;
+      fn = ls.fn;
+      referenceData = ls.referenceData;
+      likelihoodModel = ls.likelihoodModel;
     }
     // generators in TMCMC.config order: Multinomial, Multivariate, Uniform
     Json &gm = sv["Multinomial Generator"], &gv = sv["Multivariate Generator"], &gu = sv["Uniform Generator"];
@@ -3278,6 +3641,8 @@ void runExperiment(Experiment &e, Conduit &conduit) {
   } else if (stype == "sampler/tmcmc" || stype == "tmcmc") {
     tm = new TmcmcModule(js, seeds, distSeeds, distStates, resume, dist);
     st.solver.reset(tm);
+  } else if (stype == "sampler/nested" || stype == "nested") {
+    st.solver.reset(new NestedModule(js, seeds, resume, dist));
   } else if (stype == "agent/continuous/vracer" || stype == "vracer") {
     // the device rollouts + update of one learner have no exchange step:
     // several GPUs run independent replicas
@@ -3292,7 +3657,7 @@ void runExperiment(Experiment &e, Conduit &conduit) {
     st.solver.reset(new DvracerModule(js, seeds, resume));
   } else {
     fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Optimizer/MOCMAES, Sampler/TMCMC, "
-         "Agent/Continuous/VRACER and Agent/Discrete/dVRACER).",
+         "Sampler/Nested, Agent/Continuous/VRACER and Agent/Discrete/dVRACER).",
          sv["Type"].getString().c_str());
   }
   clk.mark("setup");

@@ -117,6 +117,22 @@ class _MocmaesCfg(C.Structure):
     ]
 
 
+class _NestedCfg(C.Structure):
+    _fields_ = [
+        ("variable_count", C.c_size_t), ("number_live_points", C.c_size_t), ("batch_size", C.c_size_t),
+        ("add_live_points", C.c_int), ("resampling_method", C.c_int), ("proposal_update_frequency", C.c_size_t),
+        ("ellipsoidal_scaling", C.c_double), ("min_log_evidence_delta", C.c_double),
+        ("max_effective_sample_size", C.c_double), ("max_log_likelihood", C.c_double),
+        ("prior_min", C.POINTER(C.c_double)), ("prior_max", C.POINTER(C.c_double)), ("prior_kind", C.POINTER(C.c_int)),
+        ("lower_bound", C.POINTER(C.c_double)), ("upper_bound", C.POINTER(C.c_double)),
+        ("uniform_seed", C.c_uint64), ("normal_seed", C.c_uint64), ("shuffle_seed", C.c_uint64),
+        ("likelihood", C.c_int), ("window_tries", C.c_size_t), ("max_windows", C.c_size_t), ("device", C.c_int),
+    ]
+
+
+NESTED_METHODS = {"box": 0, "ellipse": 1, "multi ellipse": 2}
+NESTED_TERMINATION = {1: "Min Log Evidence Delta", 2: "Max Effective Sample Size", 4: "Max Log Likelihood"}
+
 MOCMAES_PARENT_ORDERS = {"descending": 0, "recorded": 1}
 MOCMAES_OBJECTIVES = {"negative_rosenbrock_and_sphere": 0, "negative_rosenbrock_and_two_spheres": 1}
 
@@ -140,6 +156,11 @@ EXPORTED = [
     "kg_mocmaes_generation", "kg_mocmaes_synchronize", "kg_mocmaes_field_size", "kg_mocmaes_get_field",
     "kg_mocmaes_set_field", "kg_mocmaes_get_rng", "kg_mocmaes_set_rng", "kg_mocmaes_diagnostics",
     "kg_mocmaes_profile", "kg_mocmaes_profile_read",
+    "kg_nested_create", "kg_nested_destroy", "kg_nested_first_generation", "kg_nested_generation",
+    "kg_nested_prepare", "kg_nested_get_candidates", "kg_nested_set_evaluations", "kg_nested_eval_builtin",
+    "kg_nested_process", "kg_nested_finalize", "kg_nested_field_size", "kg_nested_get_field", "kg_nested_set_field",
+    "kg_nested_get_rng", "kg_nested_set_rng", "kg_nested_diagnostics", "kg_nested_profile",
+    "kg_nested_profile_read", "kg_nested_synchronize", "kg_nested_permutation",
     "kg_tmcmc_create", "kg_tmcmc_destroy", "kg_tmcmc_generation", "kg_tmcmc_synchronize", "kg_tmcmc_field_size",
     "kg_tmcmc_get_field", "kg_tmcmc_set_field", "kg_tmcmc_get_rng", "kg_tmcmc_set_rng", "kg_tmcmc_prepare",
     "kg_tmcmc_evaluate", "kg_tmcmc_process", "kg_tmcmc_advance", "kg_tmcmc_get_pending",
@@ -242,6 +263,24 @@ def lib():
         L.kg_mocmaes_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 4
         L.kg_mocmaes_profile.argtypes = [vp, ip]
         L.kg_mocmaes_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
+        L.kg_nested_create.argtypes = [C.POINTER(_NestedCfg), C.POINTER(vp)]
+        for f in ("kg_nested_destroy", "kg_nested_first_generation", "kg_nested_eval_builtin", "kg_nested_finalize",
+                  "kg_nested_synchronize"):
+            getattr(L, f).argtypes = [vp]
+        L.kg_nested_generation.argtypes = [vp, sz, C.POINTER(ip)]
+        L.kg_nested_prepare.argtypes = [vp, sz]
+        L.kg_nested_get_candidates.argtypes = [vp, dp, sz]
+        L.kg_nested_set_evaluations.argtypes = [vp, dp]
+        L.kg_nested_process.argtypes = [vp, sz, C.POINTER(ip), C.POINTER(ip)]
+        L.kg_nested_field_size.argtypes = [vp, cp, C.POINTER(sz)]
+        L.kg_nested_get_field.argtypes = [vp, cp, dp, sz]
+        L.kg_nested_set_field.argtypes = [vp, cp, dp, sz]
+        L.kg_nested_get_rng.argtypes = [vp, ip, vp]
+        L.kg_nested_set_rng.argtypes = [vp, ip, vp]
+        L.kg_nested_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 3
+        L.kg_nested_profile.argtypes = [vp, ip]
+        L.kg_nested_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
+        L.kg_nested_permutation.argtypes = [C.c_uint64, sz, C.POINTER(sz)]
         L.kg_tmcmc_create.argtypes = [C.POINTER(_TmcmcCfg), C.POINTER(vp)]
         for f in ("kg_tmcmc_destroy", "kg_tmcmc_synchronize", "kg_tmcmc_evaluate", "kg_tmcmc_evaluate_prior"):
             getattr(L, f).argtypes = [vp]
@@ -755,6 +794,147 @@ class MocmaesDevice:
     def profile_read(self, stage):
         ms, n = C.c_double(), C.c_size_t()
         check(self._L.kg_mocmaes_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
+def nested_permutation(seed, n):
+    """iota(n) after std::shuffle with std::default_random_engine(seed), the
+    order generatePosterior walks the dead samples in (Nested.cpp.base:584-586)."""
+    out = (C.c_size_t * max(int(n), 1))()
+    check(lib().kg_nested_permutation(int(seed) & (2**64 - 1), int(n), out))
+    return np.array(out[:int(n)], dtype=np.int64)
+
+
+class NestedDevice:
+    """One Sampler/Nested instance (resampling methods Box and Ellipse) on one
+    MI355X (kg_nested_t).  prior_min / prior_max are the two parameters of
+    every variable's prior, prior_kinds their kinds (PRIOR_KINDS names or
+    numbers; None: Uniform); lower_bound / upper_bound the variables' bounds,
+    needed for the non-Uniform ones.  likelihood: "gaussian", or None when
+    the caller sets the log-likelihoods.  Generator indices for rng_state /
+    set_rng_state: 0 Normal, 1 Uniform."""
+
+    def __init__(self, N, L, prior_min, prior_max, batch_size=1, method="Ellipse", add_live_points=True,
+                 proposal_update_frequency=1500, ellipsoidal_scaling=1.0, min_log_evidence_delta=0.01,
+                 max_effective_sample_size=10e6, max_log_likelihood=10e6, prior_kinds=None, lower_bound=None,
+                 upper_bound=None, uniform_seed=0, normal_seed=0, shuffle_seed=0, likelihood="gaussian",
+                 window_tries=0, max_windows=0, device=0):
+        lb = lib()
+        self.N, self.L, self.B = int(N), int(L), int(batch_size)
+        kinds = [0] * self.N if prior_kinds is None else [PRIOR_KINDS[k.lower()] if isinstance(k, str) else int(k)
+                                                          for k in prior_kinds]
+        self._kinds = (C.c_int * max(self.N, 1))(*kinds)
+        self._arrays = [_vec(prior_min, self.N, np.nan), _vec(prior_max, self.N, np.nan),
+                        _vec(lower_bound, self.N, -np.inf), _vec(upper_bound, self.N, np.inf)]
+        cfg = _NestedCfg()
+        cfg.variable_count, cfg.number_live_points, cfg.batch_size = self.N, self.L, self.B
+        cfg.add_live_points = int(bool(add_live_points))
+        cfg.resampling_method = NESTED_METHODS[method.lower()] if isinstance(method, str) else int(method)
+        cfg.proposal_update_frequency = int(proposal_update_frequency)
+        cfg.ellipsoidal_scaling = float(ellipsoidal_scaling)
+        cfg.min_log_evidence_delta = float(min_log_evidence_delta)
+        cfg.max_effective_sample_size = float(max_effective_sample_size)
+        cfg.max_log_likelihood = float(max_log_likelihood)
+        cfg.prior_min, cfg.prior_max, cfg.lower_bound, cfg.upper_bound = [_dptr(a) for a in self._arrays]
+        cfg.prior_kind = self._kinds
+        cfg.uniform_seed = int(uniform_seed) & (2**64 - 1)
+        cfg.normal_seed = int(normal_seed) & (2**64 - 1)
+        cfg.shuffle_seed = int(shuffle_seed) & (2**64 - 1)
+        cfg.likelihood = -1 if likelihood is None else {"gaussian": 0}[likelihood.lower()]
+        cfg.window_tries, cfg.max_windows, cfg.device = int(window_tries), int(max_windows), int(device)
+        h = C.c_void_p()
+        check(lb.kg_nested_create(C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._L = lb
+        self._rows = self.L
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.kg_nested_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # whole generations, builtin likelihood
+    def first_generation(self):
+        check(self._L.kg_nested_first_generation(self.h))
+
+    def generation(self, generation):
+        """runs one generation; returns the names of the termination criteria that hold after it"""
+        t = C.c_int(0)
+        check(self._L.kg_nested_generation(self.h, int(generation), C.byref(t)))
+        return [n for b, n in NESTED_TERMINATION.items() if t.value & b]
+
+    # stages, for likelihoods evaluated by the caller
+    def prepare(self, generation):
+        check(self._L.kg_nested_prepare(self.h, int(generation)))
+        self._rows = self.L if int(generation) == 1 else self.B
+
+    def candidates(self):
+        X = np.empty((self._rows, self.N))
+        check(self._L.kg_nested_get_candidates(self.h, _dptr(X), self.N))
+        return X
+
+    def set_evaluations(self, loglik):
+        v = np.ascontiguousarray(loglik, dtype=np.float64).reshape(-1)
+        if v.size != self._rows:
+            raise ValueError("%d log-likelihoods, expected %d" % (v.size, self._rows))
+        check(self._L.kg_nested_set_evaluations(self.h, _dptr(v)))
+
+    def process(self, generation):
+        """-> (accepted, names of the termination criteria that hold)"""
+        a, t = C.c_int(0), C.c_int(0)
+        check(self._L.kg_nested_process(self.h, int(generation), C.byref(a), C.byref(t)))
+        return bool(a.value), [n for b, n in NESTED_TERMINATION.items() if t.value & b]
+
+    def finalize(self):
+        check(self._L.kg_nested_finalize(self.h))
+
+    def synchronize(self):
+        check(self._L.kg_nested_synchronize(self.h))
+
+    # state
+    def field_size(self, name):
+        n = C.c_size_t()
+        check(self._L.kg_nested_field_size(self.h, name.encode(), C.byref(n)))
+        return n.value
+
+    def __getitem__(self, name):
+        n = self.field_size(name)
+        out = np.empty(n)
+        check(self._L.kg_nested_get_field(self.h, name.encode(), _dptr(out), n))
+        return out
+
+    def __setitem__(self, name, value):
+        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
+        check(self._L.kg_nested_set_field(self.h, name.encode(), _dptr(a), a.size))
+
+    def rng_state(self, which=0):
+        buf = C.create_string_buffer(5000)
+        check(self._L.kg_nested_get_rng(self.h, int(which), buf))
+        return buf.raw
+
+    def set_rng_state(self, state, which=0):
+        assert len(state) == 5000
+        buf = C.create_string_buffer(bytes(state), 5000)
+        check(self._L.kg_nested_set_rng(self.h, int(which), buf))
+
+    def diagnostics(self):
+        """(windows the last candidate draw used, tries it consumed, current window size in tries)"""
+        v = [C.c_size_t() for _ in range(3)]
+        check(self._L.kg_nested_diagnostics(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def profile(self, enable=True):
+        check(self._L.kg_nested_profile(self.h, int(enable)))
+
+    def profile_read(self, stage):
+        ms, n = C.c_double(), C.c_size_t()
+        check(self._L.kg_nested_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
 

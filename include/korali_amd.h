@@ -478,6 +478,10 @@ int kg_debug_mt_jump(const uint32_t *window624, uint64_t distance, uint32_t *out
  * (H[i][0] = sd[i], the reflector's entries after it), tau (N), d (N),
  * sd (N).  Runs on the host, no device needed. */
 int kg_debug_host_tridiag(size_t N, const double *C, double *H, double *tau, double *d, double *sd);
+/* The same, `count` matrices in a row on one workspace and one pool of helper
+ * threads, as the solver decomposes generation after generation: matrix k at
+ * C + k N N, its outputs at H + k N N, tau + k N, d + k N, sd + k N. */
+int kg_debug_host_tridiag_seq(size_t N, size_t count, const double *C, double *H, double *tau, double *d, double *sd);
 /* The host core's Givens chase (phase C of the eigendecomposition, GSL
  * eigen/symmv.c + qrstep.c as kg_eigen.hip's qr_chase) on the tridiagonal
  * (d[N], sd[N-1]) reps times: sorted eigenvalues (ABS_ASC) and their

@@ -2293,6 +2293,27 @@ extern "C" int kg_debug_host_tridiag(size_t N, const double *C, double *H, doubl
   return 0;
 }
 
+// `count` decompositions in a row on one workspace (one pool of helper
+// threads), as the solver runs them generation after generation: matrix k at
+// C + k N N, its outputs at H + k N N, tau + k N, d + k N, sd + k N.
+extern "C" int kg_debug_host_tridiag_seq(size_t N, size_t count, const double *C, double *H, double *tau, double *d,
+                                         double *sd) {
+  if (!C || !H || !tau || !d || !sd || N == 0 || N > 65536) {
+    kg::set_error("kg_debug_host_tridiag_seq: null argument or bad order");
+    return 1;
+  }
+  kg::HostTridiag t;
+  if (t.init((int)N)) {
+    kg::set_error("kg_debug_host_tridiag_seq: out of memory");
+    return 1;
+  }
+  for (size_t k = 0; k < count; k++) {
+    t.wake();
+    t.run(C + k * N * N, (int)N, H + k * N * N, tau + k * N, d + k * N, sd + k * N);
+  }
+  return 0;
+}
+
 // The host core's Givens chase (phase C, the product's qr_chase) on a given
 // tridiagonal, `reps` times: the sorted eigenvalues and permutation, the
 // QR-step and rotation counts, the first cs_cap rotation values and the mean

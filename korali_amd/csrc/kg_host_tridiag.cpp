@@ -57,6 +57,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -75,9 +76,15 @@
 extern unsigned long long kg_ht_phases[8];
 #define KG_HT_T(v) const unsigned long long v = __rdtsc()
 #define KG_HT_ACC(k, v) kg_ht_phases[k] += __rdtsc() - (v)
+// the multi-threaded pass, per thread (one cache line each): 0 the load of C,
+// 1 the replicated work ahead of the pass, 2 the pass over the thread's own
+// blocks, 3 the flag waits, 4 the replicated work after them
+extern unsigned long long kg_ht_mt_phases[64][8];
+#define KG_HT_MT(t, k, v) kg_ht_mt_phases[t][k] += __rdtsc() - (v)
 #else
 #define KG_HT_T(v)
 #define KG_HT_ACC(k, v)
+#define KG_HT_MT(t, k, v)
 #endif
 
 namespace kg {
@@ -258,26 +265,73 @@ std::vector<int> helper_cpus(int want, std::vector<int> &fds) {
 }
 }  // namespace
 
+// ---- the multi-threaded decomposition: every thread of the pool (the caller
+// as thread 0) runs the whole step loop of tridiag_run itself.
+//
+// Split: thread t owns the column blocks t, t + P, ... and the row blocks t,
+// t + P, ... (mt_pass in the body file) and nobody else touches them.
+// Replicated: each step's O(N) work -- column i with the pending update,
+// dnrm2, the Householder scalars, v, t1 = tau v, x = colsum + tau rowsum, the
+// x.v chain, x += alpha v, the negated copies -- is done by every thread, in
+// tridiag_run's order, on thread-private vectors.  It is one compiled
+// instance (the baseline build of this file, ht_sse2::dnrm2 / hypot_fd) on
+// identical inputs, so every thread holds identical bits, and no step vector
+// crosses between cores.
+// Crossing, per step: what a thread cannot compute alone.  Its own blocks'
+// colsum and rowsum entries (one cache line per block) and, from the owner
+// of column o, that column for the next step (nextcol).  A thread writes
+// them into its own slot of the step's parity, then stores the step's
+// sequence number to its own flag (release, a plain store: nobody else
+// writes that line).  Every thread then waits (acquire) until each peer's
+// flag has reached the sequence number and reads the peers' slots: the
+// step's one synchronisation point.  Two parities suffice: to publish step
+// s + 1 a thread needs every peer's flag for step s, so it is at most one
+// step ahead of the slowest peer, which may still be reading step s's slots
+// but has finished with those of step s - 1.
+// Sequence numbers grow across decompositions (base), so flags and slots
+// need no reset: load of C = base + 1, step i = base + 2 + i, a helper that
+// has left the loop = base + N.
 struct HostTridiagPool {
+  struct alignas(64) Flag {
+    std::atomic<uint64_t> seq{0};
+  };
   int P = 1;
   PassFn fn = nullptr;
-  // the two blocked copies of the lower triangle and the step vectors (see
-  // mt_pass); vectors padded to whole blocks + 16, zero past N
-  int N = 0, NB = 0, L = 0;
+  // the two blocked copies of the lower triangle (see mt_pass)
+  int N = 0, NB = 0, L = 0;  // L: vector length, whole blocks + 16, zero past N
   std::vector<double *> colblk, rowblk;
-  double *vecs = nullptr;
-  double *vec(int k) const { return vecs + (size_t)k * L; }
+  // per thread: 8 private step vectors, then per parity colsum, rowsum, nextcol
+  std::vector<double *> mem;
+  double *slot(int t, unsigned par) const { return mem[t] + (size_t)(8 + 3 * par) * L; }
+  std::unique_ptr<Flag[]> flag;
   std::vector<int> lockFds;  // the claimed helper cores (claim_cpu)
-  HtMtJob job;
   std::vector<std::thread> th;
+  // one decomposition: written by run_mt before epoch releases the helpers
+  uint64_t base = 0;
+  const double *C = nullptr;
+  int ldc = 0;
+  double *H = nullptr, *tau = nullptr, *d = nullptr, *sd = nullptr;
   alignas(64) std::atomic<unsigned> epoch{0};
-  alignas(64) std::atomic<unsigned> done{0};
   alignas(64) std::atomic<int> awake{0};
-  std::atomic<bool> quit{false};
+  alignas(64) std::atomic<bool> quit{false};
   long spin_us = 3000;  // KORALI_AMD_HOST_TRIDIAG_SPIN_US
   std::mutex mu;
   std::condition_variable cv;
 
+  // thread t has published seq; wait for every peer's.  false: the pool is
+  // being destroyed.
+  bool sync(int t, uint64_t seq) {
+    flag[t].seq.store(seq, std::memory_order_release);
+    for (int q = 0; q < P; q++) {
+      if (q == t) continue;
+      while (flag[q].seq.load(std::memory_order_acquire) < seq) {
+        _mm_pause();
+        if (quit.load(std::memory_order_relaxed)) return false;
+      }
+    }
+    return true;
+  }
+  bool steps(int t);
   void helper(int t, int cpu) {
     if (cpu >= 0) {
       cpu_set_t one;
@@ -286,7 +340,7 @@ struct HostTridiagPool {
       (void)pthread_setaffinity_np(pthread_self(), sizeof one, &one);
     }
     unsigned seen = 0;
-    auto last = std::chrono::steady_clock::now();  // end of the last phase this thread worked on
+    auto last = std::chrono::steady_clock::now();  // end of the last decomposition this thread worked on
     for (;;) {
       unsigned e;
       unsigned spins = 0;
@@ -309,17 +363,11 @@ struct HostTridiagPool {
       }
       seen = e;
       if (quit.load(std::memory_order_relaxed)) return;
-      fn(job, t);
-      done.fetch_add(1, std::memory_order_release);
+      const uint64_t left = base + (uint64_t)N;
+      if (!steps(t)) return;
+      flag[t].seq.store(left, std::memory_order_release);
       last = std::chrono::steady_clock::now();
     }
-  }
-  // every thread (the caller as thread 0) runs fn(job, t); returns when all are done
-  void phase() {
-    done.store(0, std::memory_order_relaxed);
-    epoch.fetch_add(1, std::memory_order_release);
-    fn(job, 0);
-    while (done.load(std::memory_order_acquire) != (unsigned)(P - 1)) _mm_pause();
   }
   void set_awake(int a) {
     {
@@ -338,43 +386,43 @@ struct HostTridiagPool {
     for (auto &t : th) t.join();
     for (double *p : colblk) std::free(p);
     for (double *p : rowblk) std::free(p);
-    std::free(vecs);
+    for (double *p : mem) std::free(p);
     for (int fd : lockFds) close(fd);
   }
 };
 
-
-namespace {
-// The multi-threaded decomposition: tridiag_run's steps (the body file) in
-// the same order, the two matrix passes of each step split over the pool
-// (mt_pass: column and row blocks), the O(N) work between them on the
-// calling thread.  Column i+1's entries, which the next Householder vector
-// needs first, come from the column block that owns them (nextcol) plus the
-// step's own rank-2 update, exactly as the single-core pass updates column i
-// ahead of its row pass.
-void run_mt(HostTridiag &w, const double *C, int ldc, double *H, double *tau, double *d, double *sd) {
-  HostTridiagPool &p = *w.pool;
-  const int N = w.N;
-  double *v = p.vec(0), *pv = p.vec(1), *x = p.vec(2), *px = p.vec(3), *npv = p.vec(4), *npx = p.vec(5),
-         *t1 = p.vec(6), *colsum = p.vec(7), *rowsum = p.vec(8), *nextcol = p.vec(9), *colb = p.vec(10);
-  for (int k = 0; k < 11; k++) std::memset(p.vec(k), 0, (size_t)p.L * sizeof(double));
-  p.set_awake(1);
-  HtMtJob &J = p.job;
-  J = HtMtJob();
-  J.N = N, J.P = p.P, J.colblk = p.colblk.data(), J.rowblk = p.rowblk.data();
+// Thread t's run through one decomposition: tridiag_run's steps (the body
+// file) in the same order.  Column i+1's entries, which the next Householder
+// vector needs first, come from the column block that owns them (nextcol)
+// plus the step's own rank-2 update, exactly as the single-core pass updates
+// column i ahead of its row pass.  Thread 0 alone writes the outputs.
+bool HostTridiagPool::steps(int t) {
+  double *const m = mem[t];
+  double *v = m, *pv = m + L, *x = m + 2 * (size_t)L, *px = m + 3 * (size_t)L, *npv = m + 4 * (size_t)L,
+         *npx = m + 5 * (size_t)L, *t1 = m + 6 * (size_t)L, *colb = m + 7 * (size_t)L;
+  std::memset(m, 0, (size_t)8 * L * sizeof(double));
+  uint64_t seq = base + 1;
+  HtMtJob J;
+  J.N = N, J.P = P, J.colblk = colblk.data(), J.rowblk = rowblk.data();
   J.kind = 1, J.C = C, J.ldc = ldc;
-  p.phase();
+  KG_HT_T(phl);
+  fn(J, t);
+  KG_HT_MT(t, 0, phl);
+  KG_HT_T(phw);
+  if (!sync(t, seq)) return false;
+  KG_HT_MT(t, 3, phw);
   J.kind = 0;
-  J.colsum = colsum, J.rowsum = rowsum, J.nextcol = nextcol;
+  const double *nextcol = nullptr;  // column i in its owner's slot of the previous step
   bool pending = false;
   for (int i = 0; i + 2 < N; i++) {
+    KG_HT_T(ph1);
     const int o = i + 1, n = N - o;
+    const unsigned par = (unsigned)(++seq & 1);
     for (int r = i; r < N; r++) {  // column i with the pending update: the Householder input
-      double m = i == 0 ? C[(size_t)r * ldc] : nextcol[r];
-      if (pending) m += npv[r] * px[i] + npx[r] * pv[i];
-      colb[r] = m;
+      double q = i == 0 ? C[(size_t)r * ldc] : nextcol[r];
+      if (pending) q += npv[r] * px[i] + npx[r] * pv[i];
+      colb[r] = q;
     }
-    d[i] = colb[i];
     double *hrow = H + (size_t)i * N;
     double ti = 0.0;
     const double xnorm = ht_sse2::dnrm2(n - 1, colb + o + 1);
@@ -391,29 +439,49 @@ void run_mt(HostTridiag &w, const double *C, int ldc, double *H, double *tau, do
         for (int c = o + 1; c < N; c++) v[c] = (colb[c] * f1) * f2;
       }
       v[o] = 1.0;
-      hrow[0] = beta;
-      for (int r = 1; r < n; r++) hrow[r] = v[o + r];
-      sd[i] = beta;
-    } else {
+      if (t == 0) {
+        hrow[0] = beta;
+        for (int r = 1; r < n; r++) hrow[r] = v[o + r];
+        sd[i] = beta;
+      }
+    } else if (t == 0) {
       for (int r = 0; r < n; r++) hrow[r] = colb[o + r];
       sd[i] = colb[o];
     }
-    tau[i] = ti;
-    for (int c = 0; c < o; c++) v[c] = 0.0;  // lanes below the submatrix
+    if (t == 0) d[i] = colb[i], tau[i] = ti;
+    // lanes below the submatrix: only those of the first active block are
+    // ever loaded (blocks below it are skipped from here on), as in tridiag_run
+    const int cb = o & ~7;
+    for (int c = cb; c < o; c++) v[c] = 0.0;
+    double *own = slot(t, par);
     J.o = o, J.pv = pv, J.px = px, J.npv = npv, J.npx = npx, J.v = v, J.t1 = t1;
+    J.colsum = own, J.rowsum = own + L, J.nextcol = own + 2 * (size_t)L;
     J.nextCol = i + 3 < N;  // the next step's column o
     J.syr2 = pending;
-    if (ti != 0.0) {
+    J.symv = ti != 0.0;
+    if (J.symv)
       for (int r = o; r < N; r++) t1[r] = ti * v[r];
-      J.symv = 1;
-      p.phase();
-      for (int c = o; c < N; c++) x[c] = colsum[c] + ti * rowsum[c];
+    KG_HT_MT(t, 1, ph1);
+    KG_HT_T(ph2);
+    fn(J, t);  // (tau = 0: the pending update alone, and the next column)
+    KG_HT_MT(t, 2, ph2);
+    KG_HT_T(ph3);
+    if (!sync(t, seq)) return false;
+    KG_HT_MT(t, 3, ph3);
+    KG_HT_T(ph4);
+    nextcol = slot((o / 8) % P, par) + 2 * (size_t)L;
+    if (ti != 0.0) {
+      for (int cb = o / 8; cb < NB; cb++) {  // block cb's sums from its owner
+        const double *cs = slot(cb % P, par), *rs = cs + L;
+        const int lo = 8 * cb > o ? 8 * cb : o, hi = 8 * cb + 8 < N ? 8 * cb + 8 : N;
+        for (int c = lo; c < hi; c++) x[c] = cs[c] + ti * rs[c];
+      }
       double xv = 0.0;
       for (int c = o; c < N; c++) xv += x[c] * v[c];
       const double alpha = -(ti / 2.0) * xv;
       for (int c = o; c < N; c++) x[c] += alpha * v[c];
-      for (int c = 0; c < o; c++) x[c] = 0.0;
-      for (int c = 0; c < p.L; c++) {
+      for (int c = cb; c < o; c++) x[c] = 0.0;
+      for (int c = cb; c < L; c++) {
         npv[c] = -1.0 * v[c];
         npx[c] = -1.0 * x[c];
       }
@@ -421,24 +489,39 @@ void run_mt(HostTridiag &w, const double *C, int ldc, double *H, double *tau, do
       std::swap(px, x);
       pending = true;
     } else {
-      J.symv = 0;
-      p.phase();  // (the pending update alone, and the next column)
       pending = false;
     }
+    KG_HT_MT(t, 4, ph4);
   }
-  if (N >= 2) {  // the last 2 x 2: from the column blocks, with the pending update
-    auto at = [&](int r, int c) { return p.colblk[c / 8][(size_t)(r - (c & ~7)) * 8 + (c & 7)]; };
-    double m[2][2];
+  if (t == 0 && N >= 2) {  // the last 2 x 2: from the column blocks, with the pending update
+    auto at = [&](int r, int c) { return colblk[c / 8][(size_t)(r - (c & ~7)) * 8 + (c & 7)]; };
+    double q2[2][2];
     for (int r = N - 2; r < N; r++)
       for (int c = N - 2; c <= r; c++) {
         double q = N > 2 ? at(r, c) : C[(size_t)r * ldc + c];
         if (pending) q += npv[r] * px[c] + npx[r] * pv[c];
-        m[r - (N - 2)][c - (N - 2)] = q;
+        q2[r - (N - 2)][c - (N - 2)] = q;
       }
-    d[N - 2] = m[0][0];
-    sd[N - 2] = m[1][0];
-    d[N - 1] = m[1][1];
+    d[N - 2] = q2[0][0];
+    sd[N - 2] = q2[1][0];
+    d[N - 1] = q2[1][1];
   }
+  return true;
+}
+
+namespace {
+// The caller's side: release the helpers into the step loop once, run it as
+// thread 0, return when every helper has left it.
+void run_mt(HostTridiag &w, const double *C, int ldc, double *H, double *tau, double *d, double *sd) {
+  HostTridiagPool &p = *w.pool;
+  p.set_awake(1);
+  p.C = C, p.ldc = ldc, p.H = H, p.tau = tau, p.d = d, p.sd = sd;
+  const uint64_t left = p.base + (uint64_t)p.N;
+  p.epoch.fetch_add(1, std::memory_order_release);
+  p.steps(0);
+  for (int q = 1; q < p.P; q++)
+    while (p.flag[q].seq.load(std::memory_order_acquire) < left) _mm_pause();
+  p.base = left;
   p.set_awake(0);
 }
 
@@ -455,8 +538,6 @@ int pool_init(HostTridiag &w, int P) {
     p->rowblk.push_back((double *)std::aligned_alloc(64, (size_t)kn * 64));
     if (!p->colblk.back() || !p->rowblk.back()) return 1;
   }
-  p->vecs = (double *)std::aligned_alloc(64, (size_t)11 * p->L * sizeof(double));
-  if (!p->vecs) return 1;
   // helpers pinned one per physical core next to the caller (unpinned, they
   // measured 3-5x slower on the box: the scheduler spreads them over CCDs);
   // fewer free cores than asked: fewer helpers (none: the single-core pass)
@@ -469,6 +550,13 @@ int pool_init(HostTridiag &w, int P) {
     std::fprintf(stderr, "\n");
   }
   if (P == 1) return 0;
+  p->flag.reset(new HostTridiagPool::Flag[P]);
+  for (int t = 0; t < P; t++) {
+    const size_t bytes = (size_t)14 * p->L * sizeof(double);
+    p->mem.push_back((double *)std::aligned_alloc(64, bytes));
+    if (!p->mem.back()) return 1;
+    std::memset(p->mem.back(), 0, bytes);
+  }
   for (int t = 1; t < P; t++) {
     const int cpu = pin ? cpus[t - 1] : -1;
     p->th.emplace_back([p, t, cpu] { p->helper(t, cpu); });
@@ -507,9 +595,9 @@ int HostTridiag::init(int N_) {
   colb = p + 6 * vec;
   t1 = p + 7 * vec;
   // threads: KORALI_AMD_HOST_TRIDIAG_THREADS, else 6 from N = 256 up, 4 from
-  // N = 128 (box, round 6: N = 512 4.16 -> 1.50 ms, 256 0.60 -> 0.33, 128
-  // 0.099 -> 0.079; more threads than that gained nothing within the box's
-  // 16-CPU share) and 1 below
+  // N = 128 and 1 below (box, medians: N = 512 4.1 -> 1.26 ms, 256 0.58 ->
+  // 0.275, 128 0.099 -> 0.062; 6 threads at N = 128 and 8 at N = 512 were
+  // within the rounds' spread of these)
   threads = N >= 256 ? 6 : (N >= 128 ? 4 : 1);
   if (const char *e = std::getenv("KORALI_AMD_HOST_TRIDIAG_THREADS")) threads = std::atoi(e);
   if (threads < 1) threads = 1;

@@ -4,9 +4,10 @@
 
 namespace kg {
 
-// One parallel phase of the multi-threaded tridiagonalisation (thread t of P
-// takes column blocks t, t + P, ... and row blocks t, t + P, ...; see
-// kg_host_tridiag.cpp).
+// One thread's share of a step of the multi-threaded tridiagonalisation
+// (thread t of P takes column blocks t, t + P, ... and row blocks t, t + P,
+// ...; see kg_host_tridiag.cpp).  Every thread fills in its own: the step
+// vectors are its private copies, the sums and nextcol its own slot.
 struct HtMtJob {
   int kind = 0;  // 0: one Householder step's pass, 1: load C into the blocks
   int N = 0, P = 1, o = 0;

@@ -490,6 +490,17 @@ int kg_debug_host_tridiag_seq(size_t N, size_t count, const double *C, double *H
  * selects the sweep with the chop test folded in.  CPU only (no device code). */
 int kg_debug_host_chase(size_t N, const double *d, const double *sd, int fused, size_t reps, double *eval, int *perm,
                         double *cs, size_t cs_cap, int *counts, double *ns_per_chase);
+/* The workgroup Cholesky every solver shares (gsl_linalg_cholesky_decomp1 in
+ * gslcblas order, csrc/kg_gsl.hpp) on `device`: in, out row-major N x N
+ * (1 <= N <= 1024).  out's lower triangle and diagonal hold the factor, or
+ * GSL's partial factor when a pivot was not positive (*failed = 1); its
+ * strict upper triangle is in's. */
+int kg_debug_cholesky(int device, size_t N, const double *in, double *out, int *failed);
+/* The univariate priors' log-density (csrc/kg_gsl.hpp) on `device`: the
+ * constant of distribution `kind` (enum kg_prior_kind) with parameters a, b
+ * in *out_const and its getLogDensity at x[0..n) in out. */
+int kg_debug_prior_logdens(int device, int kind, double a, double b, const double *x, size_t n, double *out_const,
+                           double *out);
 /* Host-only check of the TMCMC resampling (no device call): `reps`
  * consecutive gsl_ran_multinomial draws (K categories, N trials) from one
  * mt19937 seeded with `seed`, by the exact conditional-binomial walk

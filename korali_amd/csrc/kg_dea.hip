@@ -40,6 +40,7 @@
 
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
+#include "kg_gsl.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -75,11 +76,6 @@ __global__ void __launch_bounds__(256) k_dea_init(int N, size_t tot, const doubl
   const double v = lb[d] + wu;
   cand[e] = v;
   X[e] = v;
-}
-
-__global__ void k_dea_fill(double *p, size_t n, double v) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) p[e] = v;
 }
 
 // setInitialConfiguration's scalars (DEA.cpp.base:41-48); the two rates keep
@@ -228,9 +224,6 @@ __global__ void __launch_bounds__(DEA_TPB) k_dea_propose(int N, int P, int paren
     sc->infeasibleSampleCount += infeasible;
   }
 }
-
-// KORALI_START of every sample (DEA.cpp.base:77) for host-evaluated objectives
-__global__ void k_dea_add_evals(CmaesScalars *osc, double n) { osc->modelEvaluationCount += n; }
 
 // updateSolver up to the accept decisions (DEA.cpp.base:198-256), one
 // workgroup: the first index of the maximum (std::max_element), the shifted
@@ -550,7 +543,7 @@ int kg_dea_initialize(kg_dea_t h) {
   hipLaunchKernelGGL(k_dea_init, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->N, tot, h->lb, h->ub,
                      h->ubuf, h->X, h->cand);
   KG_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_dea_fill, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, h->F, P, -INFINITY);
+  hipLaunchKernelGGL(k_fill, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, h->F, P, -INFINITY);
   KG_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_dea_init_scalars, dim3(1), dim3(1), 0, h->stream, h->sc);
   KG_HIP(hipGetLastError());
@@ -655,7 +648,8 @@ int kg_dea_set_fitness(kg_dea_t h, const double *F) {
     KG_CHECK(std::isfinite(F[i]), "Non finite value of function evaluation detected for sample " + std::to_string(i));
   DeaStage st(h, "evaluate");
   KG_HIP(hipMemcpyAsync(h->F, F, h->P * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_dea_add_evals, dim3(1), dim3(1), 0, h->stream, h->osc, (double)h->P);
+  // KORALI_START of every sample (DEA.cpp.base:77); kg_cmaes.hip's kernel on the same CmaesScalars
+  hipLaunchKernelGGL(k_add_evals, dim3(1), dim3(1), 0, h->stream, h->osc, (double)h->P);
   KG_HIP(hipGetLastError());
   KG_HIP(hipStreamSynchronize(h->stream));  // F is the caller's
   return 0;

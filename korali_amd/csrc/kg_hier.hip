@@ -28,6 +28,7 @@
 
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
+#include "kg_gsl.hpp"
 
 namespace kg {
 namespace hier {
@@ -71,45 +72,12 @@ struct Layout {
   bool sidePending = false;
 };
 
-// the distributions' updateDistribution constants (uniform.cpp.base:38-44,
-// normal :42, exponential getLogDensity :16, laplace :41, cauchy :41,
-// logNormal :45)
-__device__ inline double prior_const(int kind, double a, double b) {
-  const double pi = 3.14159265358979323846;
-  switch (kind) {
-    case KG_PRIOR_NORMAL:
-    case KG_PRIOR_LOGNORMAL: return -0.5 * log_cr(2 * pi) - log_cr(b);
-    case KG_PRIOR_EXPONENTIAL: return -log_cr(b);
-    case KG_PRIOR_LAPLACE: return -log_cr(2. * b);
-    case KG_PRIOR_CAUCHY: return -log_cr(b * pi);
-    default: return (b - a <= 0.0) ? (double)NAN : -log_cr(b - a);
-  }
-}
-
-__device__ inline bool prior_invalid(int kind, double b) {
-  return (kind == KG_PRIOR_NORMAL || kind == KG_PRIOR_LOGNORMAL || kind == KG_PRIOR_LAPLACE ||
-          kind == KG_PRIOR_CAUCHY) && b <= 0.0;
-}
-
-// getLogDensity of the six distributions; lx = log_cr(x) where kind is LogNormal and x > 0
-__device__ inline double logdens(int kind, double x, double lx, double a, double b, double cn) {
-  switch (kind) {
-    case KG_PRIOR_NORMAL: {
-      const double d = (x - a) / b;
-      return cn - 0.5 * d * d;
-    }
-    case KG_PRIOR_EXPONENTIAL:
-      if (x - a < 0) return -INFINITY;
-      return cn - (x - a) / b;
-    case KG_PRIOR_LAPLACE: return cn - fabs(x - a) / b;
-    case KG_PRIOR_CAUCHY: return cn - log_cr(1. + (x - a) * (x - a) / (b * b));
-    case KG_PRIOR_LOGNORMAL: {
-      if (x <= 0) return -INFINITY;
-      const double d = (lx - a) / b;
-      return cn - lx - 0.5 * d * d;
-    }
-    default: return (x >= a && x <= b) ? cn : -INFINITY;
-  }
+// prior_const of a conditional prior, whose parameters may come from a
+// sample: a Uniform of no or negative width has the constant NaN here (the
+// guard is this file's alone)
+__device__ __forceinline__ double conditional_const(int kind, double a, double b) {
+  const double cn = prior_const(kind, a, b);
+  return (kind == KG_PRIOR_UNIFORM && b - a <= 0.0) ? (double)NAN : cn;
 }
 
 // set-up: Psi — log_cr of the LogNormal columns; ThetaNew — every row's
@@ -131,7 +99,7 @@ __global__ void k_hier_setup(int mode, int D, size_t R, int W, const int *__rest
     const double b = psrc[2 * k + 1] >= 0 ? rows[r * W + psrc[2 * k + 1]] : pconst[2 * k + 1];
     A[e] = a;
     B[e] = b;
-    Cn[e] = prior_const(kind[k], a, b);
+    Cn[e] = conditional_const(kind[k], a, b);
   }
 }
 
@@ -169,8 +137,8 @@ __global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t 
       const double b = psrc[2 * k + 1] >= 0 ? x[psrc[2 * k + 1]] : pconst[2 * k + 1];
       sa[k] = a;
       sb[k] = b;
-      sc[k] = prior_const(sk[k], a, b);
-      if (g == 0 && prior_invalid(sk[k], b))
+      sc[k] = conditional_const(sk[k], a, b);
+      if (g == 0 && prior_scale_invalid(sk[k], b))
         atomicMin(status, ((unsigned long long)c << 32) | (unsigned long long)k);
     } else {  // the point itself and, for LogNormal priors, its logarithm
       const double v = x[k];
@@ -186,15 +154,15 @@ __global__ void __launch_bounds__(TPB) k_hier_group(int D, int G, int W, size_t 
     double v;
     if (MODE == KG_HIER_PSI) {
       v = base[r];  // psi.cpp.base:132
-      for (int k = 0; k < D; k++) v += logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
+      for (int k = 0; k < D; k++) v += prior_logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
     } else if (MODE == MODE_THETA_DEN) {
       v = 0.;  // theta.cpp.base:73-77: the sub-sample's log-prior (base, not negated) comes off last
-      for (int k = 0; k < D; k++) v += logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
+      for (int k = 0; k < D; k++) v += prior_logdens(sk[k], A[(size_t)k * R + r], B[(size_t)k * R + r], sa[k], sb[k], sc[k]);
       v -= base[r];
     } else {
       v = 0.;  // thetaNew.cpp.base:48, theta.cpp.base:116
       for (int k = 0; k < D; k++)
-        v += logdens(sk[k], sa[k], sb[k], A[(size_t)k * R + r], B[(size_t)k * R + r], Cn[(size_t)k * R + r]);
+        v += prior_logdens(sk[k], sa[k], sb[k], A[(size_t)k * R + r], B[(size_t)k * R + r], Cn[(size_t)k * R + r]);
       if (MODE == KG_HIER_THETA) v -= den[r];  // theta.cpp.base:120
     }
     return v;

@@ -39,6 +39,7 @@
 
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
+#include "kg_gsl.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -99,11 +100,6 @@ __device__ inline double merged(const double *__restrict__ Vc, const double *__r
   return i < P ? Vc[(size_t)i * K + k] : Vp[(size_t)(i - P) * K + k];
 }
 
-__global__ void k_mo_fill(double *p, size_t n, double v) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) p[e] = v;
-}
-
 // setInitialConfiguration's parents (:110-124): sigma = sqrt(trace / N), the
 // covariance diag(sdev_d^2 / sigma^2), everything else 0
 __global__ void k_mo_init_parents(int N, int mu, const double *__restrict__ sdev, double sigma, double target,
@@ -142,8 +138,8 @@ __global__ void __launch_bounds__(MO_TPB) k_mo_pick(int P, int mu, const double 
 
 // ------------------------------------------------------------------ factor
 // sampleSingle :198-207: gsl_linalg_cholesky_decomp1 in place on a copy of the
-// parent's covariance, then gsl_matrix_scale by the parent's sigma; the loop
-// order is k_tm_cholesky's (GSL's Level-2 form with gslcblas dgemv order).
+// parent's covariance (block_cholesky_gsl), then gsl_matrix_scale by the
+// parent's sigma.
 // One workgroup per parent that was drawn; the matrix lives in LDS, N x (N+1).
 // The lower triangle is written transposed (LT[j * N + r] = sigma * L[r][j]) so
 // that the draw's threads, one per row r, read consecutive addresses.
@@ -154,39 +150,13 @@ __global__ void __launch_bounds__(MO_TPB) k_mo_factor(int N, const double *__res
                                                       const double *__restrict__ pSg, const int *__restrict__ used,
                                                       double *__restrict__ LT, MoScalars *sc) {
   extern __shared__ double A[];  // N x (N+1)
-  __shared__ double f;
-  __shared__ int failed;
   const int p = blockIdx.x;
   if (!used[p]) return;
   const int S = N + 1;
   const double *cov = pC + (size_t)p * N * N;
   for (int e = threadIdx.x; e < N * N; e += blockDim.x) A[(e / N) * S + e % N] = cov[e];
-  if (threadIdx.x == 0) failed = 0;
   __syncthreads();
-  for (int j = 0; j < N; j++) {
-    if (j > 0) {
-      for (int r = j + threadIdx.x; r < N; r += blockDim.x) {
-        double temp = 0.0;
-        for (int i = 0; i < j; i++) temp += A[j * S + i] * A[r * S + i];
-        A[r * S + j] += -1.0 * temp;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      double ajj = A[j * S + j];
-      if (ajj <= 0.0) {
-        failed = 1;
-      } else {
-        ajj = sqrt(ajj);
-        f = 1.0 / ajj;
-      }
-    }
-    __syncthreads();
-    if (failed) break;
-    for (int r = j + threadIdx.x; r < N; r += blockDim.x) A[r * S + j] *= f;
-    __syncthreads();
-  }
-  if (failed && threadIdx.x == 0) {
+  if (block_cholesky_gsl(A, N, S) && threadIdx.x == 0) {
     atomicOr(&sc->errors, KG_ERR_CHOLESKY);
     sc->failedParent = p;
   }
@@ -1024,7 +994,7 @@ int mo_archive_reserve(kg_mocmaes_s *h, size_t rows) {
 
 int mo_fill(kg_mocmaes_s *h, double *p, size_t n, double v) {
   if (!n) return 0;
-  hipLaunchKernelGGL(k_mo_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p, n, v);
+  hipLaunchKernelGGL(k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, p, n, v);
   KG_HIP(hipGetLastError());
   return 0;
 }

@@ -37,6 +37,7 @@
 
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
+#include "kg_gsl.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -60,53 +61,18 @@ struct NsChain {
   int done;
 };
 
-// one variable's prior log-density (the distributions' getLogDensity, as
-// k_tm_evaluate evaluates them): a, b the two parameters, c the constant
-__device__ inline double ns_logdens(int kind, double a, double b, double c, double x) {
-  switch (kind) {
-    case KG_PRIOR_NORMAL: {
-      const double z = (x - a) / b;
-      return c - 0.5 * z * z;
-    }
-    case KG_PRIOR_EXPONENTIAL: {
-      const double y = x - a;
-      return y < 0 ? -INFINITY : c - y / b;
-    }
-    case KG_PRIOR_LAPLACE: return c - fabs(x - a) / b;
-    case KG_PRIOR_CAUCHY: {
-      const double y = x - a;
-      return c - log_cr(1. + y * y / (b * b));
-    }
-    case KG_PRIOR_LOGNORMAL: {
-      if (x <= 0) return -INFINITY;
-      const double lx = log_cr(x), z = (lx - a) / b;
-      return c - lx - 0.5 * z * z;
-    }
-    default: return (x >= a && x <= b) ? c : -INFINITY;
-  }
-}
-
 __global__ void k_ns_prior_const(int N, const double *__restrict__ pmin, const double *__restrict__ pmax,
                                  const int *__restrict__ kind, const double *__restrict__ width,
                                  double *__restrict__ cst, double *__restrict__ logWidth) {
   const int d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= N) return;
-  const double pi = 3.14159265358979323846, b = pmax[d];
-  double c;
-  switch (kind[d]) {
-    case KG_PRIOR_NORMAL:
-    case KG_PRIOR_LOGNORMAL: c = -0.5 * log_cr(2 * pi) - log_cr(b); break;
-    case KG_PRIOR_EXPONENTIAL: c = -log_cr(b); break;
-    case KG_PRIOR_LAPLACE: c = -log_cr(2. * b); break;
-    case KG_PRIOR_CAUCHY: c = -log_cr(b * pi); break;
-    default: c = -log_cr(b - pmin[d]);
-  }
-  cst[d] = c;
+  cst[d] = prior_const(kind[d], pmin[d], pmax[d]);
   logWidth[d] = log_cr(width[d]);  // :373
 }
 
-// priorTransform (:275-279), evaluateLogPrior, logPriorWeight (:366-376) and
-// the builtin log-likelihood of n rows; lik < 0: the caller sets logLikelihood
+// priorTransform (:275-279), evaluateLogPrior (prior_logdens per variable),
+// logPriorWeight (:366-376) and the builtin log-likelihood of n rows;
+// lik < 0: the caller sets logLikelihood
 __global__ void __launch_bounds__(NS_TPB) k_ns_evaluate(int N, int n, int lik, const double *__restrict__ X,
                                                         const double *__restrict__ lower,
                                                         const double *__restrict__ width,
@@ -125,7 +91,7 @@ __global__ void __launch_bounds__(NS_TPB) k_ns_evaluate(int N, int n, int lik, c
     const double xw = x[d] * width[d];
     const double v = lower[d] + xw;
     t[d] = v;
-    const double ld = ns_logdens(kind[d], pmin[d], pmax[d], cst[d], v);
+    const double ld = prior_logdens(kind[d], v, pmin[d], pmax[d], cst[d]);
     lp += ld;
     lpw += ld;
     lpw += logWidth[d];
@@ -234,8 +200,8 @@ __global__ void __launch_bounds__(NS_TPB) k_ns_cov(int N, int L, int diag, doubl
 // workgroup: LU with partial pivoting (first maximal pivot, unblocked,
 // right-looking) in LDS -> det, invCov column by column (forward, then back
 // substitution of the permuted unit vector; one thread per column); the
-// Level-2 Cholesky of gsl_linalg_cholesky_decomp1 into axes (upper triangle:
-// the original matrix); the largest Mahalanobis distance over the live set;
+// Level-2 Cholesky of gsl_linalg_cholesky_decomp1 (block_cholesky_gsl) into
+// axes (upper triangle: the original matrix); the largest Mahalanobis distance over the live set;
 // the enlargement and the rescalings of :852-875.
 __global__ void __launch_bounds__(NS_TPB) k_ns_factor(int N, int L, int diag, const double *__restrict__ live,
                                                       const double *__restrict__ mean, double *__restrict__ cov,
@@ -315,29 +281,7 @@ __global__ void __launch_bounds__(NS_TPB) k_ns_factor(int N, int L, int diag, co
     }
   }
   __syncthreads();
-  // Cholesky, lower triangle of axes in place
-  bool bad = false;
-  for (int j = 0; j < N; j++) {
-    if (j > 0) {
-      for (int r = j + tid; r < N; r += NS_TPB) {
-        double temp = 0.0;
-        for (int i = 0; i < j; i++) temp += axes[j * N + i] * axes[r * N + i];
-        axes[r * N + j] += -1.0 * temp;
-      }
-      __syncthreads();
-    }
-    double ajj = axes[j * N + j];
-    if (ajj <= 0.0) {
-      bad = true;
-      break;
-    }
-    ajj = sqrt(ajj);
-    const double f = 1.0 / ajj;
-    __syncthreads();
-    for (int r = j + tid; r < N; r += NS_TPB) axes[r * N + j] *= f;
-    __syncthreads();
-  }
-  if (bad) {
+  if (block_cholesky_gsl(axes, N, N)) {  // the lower triangle of axes in place
     if (tid == 0) el->errors |= KG_ERR_CHOLESKY;
     return;
   }

@@ -36,6 +36,7 @@
 
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
+#include "kg_gsl.hpp"
 #include "kg_mtmcmc.hpp"
 #include "kg_rng.hpp"
 
@@ -59,45 +60,17 @@ struct CvPoints {
 };
 
 // ------------------------------------------------------------ Cholesky
-// gsl_linalg_cholesky_decomp (GSL 2.6 linalg/cholesky.c, Level-2 form, with
-// gslcblas dgemv order: temp = sum_i x[i] A[r][i] from 0, y += alpha*temp),
-// called in place on the covariance (TMCMC.cpp.base:205-213).  With
-// gsl_set_error_handler_off (engine.cpp:30) a non-positive pivot returns
-// early and leaves the partially factored matrix, which the reference then
-// uses as it is: mirrored here.
+// gsl_linalg_cholesky_decomp called in place on the covariance
+// (TMCMC.cpp.base:205-213): block_cholesky_gsl on an LDS copy.  A
+// non-positive pivot returns early and leaves the partially factored matrix,
+// which the reference then uses as it is: mirrored here.
 __global__ void __launch_bounds__(256) k_tm_cholesky(int N, const double *__restrict__ cov, double *__restrict__ L,
                                                      TmDev *dev) {
   extern __shared__ double A[];  // N x (N+1)
-  __shared__ double f;
-  __shared__ int failed;
   const int S = N + 1;
   for (int e = threadIdx.x; e < N * N; e += blockDim.x) A[(e / N) * S + e % N] = cov[e];
-  if (threadIdx.x == 0) failed = 0;
   __syncthreads();
-  for (int j = 0; j < N; j++) {
-    if (j > 0) {
-      for (int r = j + threadIdx.x; r < N; r += blockDim.x) {
-        double temp = 0.0;
-        for (int i = 0; i < j; i++) temp += A[j * S + i] * A[r * S + i];
-        A[r * S + j] += -1.0 * temp;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      double ajj = A[j * S + j];
-      if (ajj <= 0.0) {
-        failed = 1;
-      } else {
-        ajj = sqrt(ajj);
-        f = 1.0 / ajj;
-      }
-    }
-    __syncthreads();
-    if (failed) break;
-    for (int r = j + threadIdx.x; r < N; r += blockDim.x) A[r * S + j] *= f;
-    __syncthreads();
-  }
-  if (!failed) {  // gsl_matrix_transpose_tricpy: upper = lower^T
+  if (!block_cholesky_gsl(A, N, S)) {  // gsl_matrix_transpose_tricpy: upper = lower^T
     for (int e = threadIdx.x; e < N * N; e += blockDim.x) {
       const int i = e / N, j = e % N;
       if (i < j) A[i * S + j] = A[j * S + i];
@@ -204,40 +177,7 @@ __global__ void k_tm_evaluate(int N, int P, int lik, const double *__restrict__ 
   if (c >= P || !pend[c]) return;
   const double *x = cand + (size_t)c * N;
   double lp = 0.0;
-  for (int d = 0; d < N; d++) {
-    const double a = pmin[d], b = pmax[d], c = negLogWidth[d];
-    switch (vkind[d]) {
-      case KG_PRIOR_NORMAL: {
-        const double z = (x[d] - a) / b;
-        lp += c - 0.5 * z * z;
-        break;
-      }
-      case KG_PRIOR_EXPONENTIAL: {  // exponential.cpp.base: -log(mean) - (x - location) / mean
-        const double y = x[d] - a;
-        lp += y < 0 ? -INFINITY : c - y / b;
-        break;
-      }
-      case KG_PRIOR_LAPLACE:  // laplace.cpp.base: aux - |x - mean| / width
-        lp += c - fabs(x[d] - a) / b;
-        break;
-      case KG_PRIOR_CAUCHY: {  // cauchy.cpp.base: aux - log(1 + (x - loc)^2 / scale^2)
-        const double y = x[d] - a;
-        lp += c - log_cr(1. + y * y / (b * b));
-        break;
-      }
-      case KG_PRIOR_LOGNORMAL: {  // logNormal.cpp.base: aux - log x - 0.5 d^2, d = (log x - mu) / sigma
-        if (x[d] <= 0) {
-          lp += -INFINITY;
-        } else {
-          const double lx = log_cr(x[d]), z = (lx - a) / b;
-          lp += c - lx - 0.5 * z * z;
-        }
-        break;
-      }
-      default:
-        lp += (x[d] >= a && x[d] <= b) ? c : -INFINITY;
-    }
-  }
+  for (int d = 0; d < N; d++) lp += prior_logdens(vkind[d], x[d], pmin[d], pmax[d], negLogWidth[d]);
   candLP[c] = lp;
   double ll = -INFINITY;
   if (!(isinf(lp) && lp < 0)) {
@@ -266,23 +206,11 @@ __global__ void k_tm_pend_init(int P, int lo, int hi, unsigned char *__restrict_
   if (c < P) pend[c] = (c >= lo && c < hi) ? 1 : 0;
 }
 
-// each variable's log-density constant (the distributions' updateDistribution
-// / getLogDensity): Uniform -log(b - a); Normal and LogNormal -0.5 log(2 pi)
-// - log(sd); Exponential -log(mean); Laplace -log(2 width); Cauchy
-// -log(scale pi)
+// each variable's log-density constant (prior_const)
 __global__ void k_tm_neglogwidth(int N, const double *__restrict__ pmin, const double *__restrict__ pmax,
                                  const int *__restrict__ vkind, double *__restrict__ out) {
   const int d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= N) return;
-  const double pi = 3.14159265358979323846, b = pmax[d];
-  switch (vkind[d]) {
-    case KG_PRIOR_NORMAL:
-    case KG_PRIOR_LOGNORMAL: out[d] = -0.5 * log_cr(2 * pi) - log_cr(b); break;
-    case KG_PRIOR_EXPONENTIAL: out[d] = -log_cr(b); break;
-    case KG_PRIOR_LAPLACE: out[d] = -log_cr(2. * b); break;
-    case KG_PRIOR_CAUCHY: out[d] = -log_cr(b * pi); break;
-    default: out[d] = -log_cr(b - pmin[d]);
-  }
+  if (d < N) out[d] = prior_const(vkind[d], pmin[d], pmax[d]);
 }
 
 // processCandidate + calculateAcceptanceProbability + updateDatabase
@@ -1518,11 +1446,6 @@ __global__ void k_tm_expand(int N, int P, int count, const unsigned *__restrict_
   }
 }
 
-__global__ void k_tm_fill(double *p, size_t n, double v) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
 // ------------------------------------------------------- chain sharding
 // After its chains finished, a shard's rows of the database, leaders and
 // candidates (+ log-likelihoods / log-priors) and its accepted count travel
@@ -2106,11 +2029,8 @@ int tm_hier_status(kg_tmcmc_s *h) {
     double v = pconst[2 * k + 1];
     if (psrc[2 * k + 1] >= 0)
       KG_HIP(hipMemcpy(&v, L.lastX + c * L.lastLd + psrc[2 * k + 1], sizeof(double), hipMemcpyDeviceToHost));
-    const char *what = kind[k] == KG_PRIOR_NORMAL      ? "Standard Deviation parameter of Normal"
-                       : kind[k] == KG_PRIOR_LOGNORMAL ? "Sigma parameter of LogNormal"
-                       : kind[k] == KG_PRIOR_LAPLACE   ? "Width parameter of Laplace"
-                                                       : "Scale parameter of Cauchy";
-    snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (chain %zu, conditional prior %d)", what, v, c, k);
+    snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (chain %zu, conditional prior %d)",
+             prior_scale_name(kind[k]), v, c, k);
   }
   set_error(msg);
   return 1;
@@ -2559,7 +2479,7 @@ int tm_initialize(kg_tmcmc_s *h) {
   h->coefficientOfVariation = 0.0;
   h->maxLoglikelihood = -INFINITY;
   h->chainCount = h->P;
-  hipLaunchKernelGGL(k_tm_fill, dim3(nblk(h->P, 256)), dim3(256), 0, h->stream, h->chainLen, (size_t)h->P, 1.0);
+  hipLaunchKernelGGL(k_fill, dim3(nblk(h->P, 256)), dim3(256), 0, h->stream, h->chainLen, (size_t)h->P, 1.0);
   KG_HIP(hipGetLastError());
   h->hLen.assign(h->P, 1u);
   return 0;
@@ -3281,17 +3201,12 @@ static int tm_hier_check_rows(int D, const int *kind, const int *param_index, co
                               const double *rows, size_t R, size_t W) {
   for (size_t r = 0; r < R; r++)
     for (int k = 0; k < D; k++) {
-      const int kd = kind[k], ix = param_index[2 * k + 1];
+      const int ix = param_index[2 * k + 1];
       const double b = ix >= 0 ? rows[r * W + ix] : param_const[2 * k + 1];
-      if ((kd == KG_PRIOR_NORMAL || kd == KG_PRIOR_LOGNORMAL || kd == KG_PRIOR_LAPLACE || kd == KG_PRIOR_CAUCHY) &&
-          b <= 0.0) {
+      if (prior_scale_invalid(kind[k], b)) {
         char msg[200];
         snprintf(msg, sizeof msg, "Incorrect %s distribution: %f. (Psi sample %zu, conditional prior %d)",
-                 kd == KG_PRIOR_NORMAL      ? "Standard Deviation parameter of Normal"
-                 : kd == KG_PRIOR_LOGNORMAL ? "Sigma parameter of LogNormal"
-                 : kd == KG_PRIOR_LAPLACE   ? "Width parameter of Laplace"
-                                            : "Scale parameter of Cauchy",
-                 b, r, k);
+                 prior_scale_name(kind[k]), b, r, k);
         KG_CHECK(false, msg);
       }
     }

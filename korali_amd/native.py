@@ -170,6 +170,7 @@ EXPORTED = [
     "kg_tmcmc_profile", "kg_tmcmc_profile_read", "kg_debug_mt_jump", "kg_debug_multinomial", "kg_debug_cartpole",
     "kg_debug_cartpole_at",
     "kg_debug_host_tridiag", "kg_debug_host_tridiag_seq", "kg_debug_host_chase",
+    "kg_debug_cholesky", "kg_debug_prior_logdens",
     # VRACER (korali_amd/vracer.py binds their argument types)
     "kg_vracer_create", "kg_vracer_create_discrete", "kg_vracer_destroy", "kg_vracer_hyperparameter_count", "kg_vracer_field_size",
     "kg_vracer_get_field", "kg_vracer_set_field", "kg_vracer_get_scalar", "kg_vracer_set_scalar",
@@ -213,6 +214,8 @@ def lib():
         L.kg_debug_host_tridiag.argtypes = [sz, vp, vp, vp, vp, vp]
         L.kg_debug_host_tridiag_seq.argtypes = [sz, sz, vp, vp, vp, vp, vp]
         L.kg_debug_host_chase.argtypes = [sz, vp, vp, C.c_int, sz, vp, vp, vp, sz, vp, vp]
+        L.kg_debug_cholesky.argtypes = [C.c_int, sz, vp, vp, vp]
+        L.kg_debug_prior_logdens.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, vp, sz, vp, vp]
         L.kg_cmaes_generation.argtypes = [vp, sz, ip]
         L.kg_cmaes_field_size.argtypes = [vp, cp, C.POINTER(sz)]
         L.kg_cmaes_get_field.argtypes = [vp, cp, dp, sz]

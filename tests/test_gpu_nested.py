@@ -83,12 +83,25 @@ def test_every_field_matches_the_restatement(method, L, N, B, scaling):
     run_both(dev, ref)
 
 
-def test_non_uniform_priors():
-    """Normal and LogNormal priors inside finite bounds (:77-90, logPriorWeight :366-376)"""
-    kw = dict(prior_min=[0.0, 0.0, -1.0], prior_max=[1.0, 0.5, 2.0], prior_kinds=["Normal", "LogNormal", "Uniform"],
-              lower_bound=[-3.0, 0.1, 0.0], upper_bound=[3.0, 4.0, 0.0])
+NON_UNIFORM = {
+    "normal-lognormal-uniform": (
+        dict(prior_min=[0.0, 0.0, -1.0], prior_max=[1.0, 0.5, 2.0], prior_kinds=["Normal", "LogNormal", "Uniform"],
+             lower_bound=[-3.0, 0.1, 0.0], upper_bound=[3.0, 4.0, 0.0]),
+        [-3.0, 0.1, -1.0], [6.0, 3.9, 3.0]),
+    # the Exponential's bounds start below its location: the first live set has -inf log-priors
+    "exponential-laplace-cauchy": (
+        dict(prior_min=[0.0, 0.5, 0.0], prior_max=[1.0, 0.7, 0.5], prior_kinds=["Exponential", "Laplace", "Cauchy"],
+             lower_bound=[-0.5, -2.0, -3.0], upper_bound=[4.0, 3.0, 3.0]),
+        [-0.5, -2.0, -3.0], [4.5, 5.0, 6.0]),
+}
+
+
+@pytest.mark.parametrize("priors", sorted(NON_UNIFORM))
+def test_non_uniform_priors(priors):
+    """non-Uniform priors inside finite bounds (:77-90, logPriorWeight :366-376)"""
+    kw, lower, width = NON_UNIFORM[priors]
     dev, ref = pair("Ellipse", 50, 3, 4, **kw)
-    assert ref.lower == [-3.0, 0.1, -1.0] and ref.width == [6.0, 3.9, 3.0]
+    assert ref.lower == lower and ref.width == width
     run_both(dev, ref)
 
 

@@ -22,8 +22,10 @@ def main():
     subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
     out = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
-    for blk in out.split(".name:")[1:]:
-        name = blk.split("\n")[0].strip()
+    # one list entry per kernel ("  - .agpr_count: ..."); its keys are sorted,
+    # so .group_segment_fixed_size stands before .name and .vgpr_count after it
+    for blk in re.split(r"\n  - ", out.split("amdhsa.kernels:")[1])[1:]:
+        name = (re.search(r"\n    \.name:\s+(\S+)", blk) or [None, ""])[1]
         if pat in name:
             get = lambda k: (re.search(rf"\.{k}:\s+(\d+)", blk) or [None, "?"])[1]
             print(f"{name[:70]:70s} vgpr {get('vgpr_count'):>4} agpr {get('agpr_count'):>4} "

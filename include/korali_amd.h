@@ -28,6 +28,9 @@
  *                         solver state incl. RNG "Range" (distribution.cpp.base:10-62)
  *
  *   kg_tmcmc_*            TMCMC::runGeneration             TMCMC.cpp.base:107-157
+ *   kg_supervisor_*       DeepSupervisor::runGeneration / getEvaluation
+ *                         deepSupervisor.cpp.base:97-187 (float32 networks; the
+ *                         section below cites each layer and optimizer)
  *
  * Conventions: every function returns 0 on success and non-zero on error;
  * kg_last_error() returns the message (thread-local).  No C++ exceptions or
@@ -1012,6 +1015,109 @@ int kg_nested_synchronize(kg_nested_t h); /* waits and reports device-side error
 /* out[0..n) = iota(n) after std::shuffle(..., std::default_random_engine(seed))
  * (Nested.cpp.base:584-586).  Host only. */
 int kg_nested_permutation(uint64_t seed, size_t n, size_t *out);
+
+/* ------------------------------------------------------- DeepSupervisor
+ * Learner/DeepSupervisor on a Supervised Learning problem (feed-forward,
+ * float32, one timestep), the whole training step on the device:
+ *
+ *   kg_supervisor_create            DeepSupervisor::initialize  deepSupervisor.cpp.base:9-95
+ *                                   (NeuralNetwork::initialize neuralNetwork.cpp.base:14-160:
+ *                                    the layer pipelines of both batch sizes)
+ *   kg_supervisor_set_training_data the problem's _inputData / _solutionData
+ *                                   (supervisedLearning.cpp.base:18-48 checks them)
+ *   kg_supervisor_train             DeepSupervisor::runGeneration's step loop :106-160
+ *                                   (Linear forward / backward linear.cpp.base:219-232,
+ *                                    :284-292, :337-350; Activation activation.cpp.base:147-209,
+ *                                    :270-314; Output output.cpp.base:115-232; the L2 term
+ *                                    :147-153; fAdam.cpp:64-91, fAdaBelief.cpp:25-53,
+ *                                    fMadGrad.cpp:54-74, fRMSProp.cpp:52-69, fAdagrad.cpp:38-54)
+ *   kg_supervisor_forward           DeepSupervisor::getEvaluation :177-187
+ *   kg_supervisor_backward_direct   NeuralNetwork::backward on given output gradients
+ *                                   (the "Direct Gradient" loss, :140-141)
+ *   kg_supervisor_{get,set}_field   getHyperparameters / setHyperparameters :163-175,
+ *                                   the optimizer's vectors, each layer's values
+ *
+ * Layers are numbered as the reference numbers them: 0 is the input, then the
+ * given layers, the Output layer last.  Hyperparameters and their gradient are
+ * one float vector each in the reference's layout, [W (OC x IC), b] per Linear
+ * layer.  The dense products run on the FP32 matrix cores; every reduction has
+ * a fixed order (no floating-point atomics): equal states give equal bits. */
+typedef struct kg_supervisor_s *kg_supervisor_t;
+enum kg_supervisor_layer_type { KG_SV_LINEAR = 0, KG_SV_ACTIVATION = 1 };
+enum kg_supervisor_function {
+  KG_SV_TANH = 0,     /* Elementwise/Tanh */
+  KG_SV_RELU = 1,     /* Elementwise/ReLU (alpha: the negative slope) */
+  KG_SV_LOGISTIC = 2, /* Elementwise/Logistic */
+  KG_SV_SOFTRELU = 3, /* Elementwise/SoftReLU */
+  KG_SV_SOFTSIGN = 4, /* Elementwise/SoftSign */
+  KG_SV_ELINEAR = 5,  /* Elementwise/Linear (alpha x + beta) */
+  KG_SV_LOG = 6,      /* Elementwise/Log */
+  KG_SV_SOFTMAX = 7   /* Softmax (backward: the diagonal term, activation.cpp.base:311-313) */
+};
+enum kg_supervisor_mask { KG_SV_IDENTITY = 0, KG_SV_ABSOLUTE = 1, KG_SV_SOFTPLUS = 2, KG_SV_MASK_TANH = 3, KG_SV_SIGMOID = 4 };
+enum kg_supervisor_optimizer { KG_SV_ADAM = 0, KG_SV_ADABELIEF = 1, KG_SV_MADGRAD = 2, KG_SV_RMSPROP = 3, KG_SV_ADAGRAD = 4 };
+enum kg_supervisor_loss { KG_SV_MEAN_SQUARED_ERROR = 0, KG_SV_DIRECT_GRADIENT = 1 };
+typedef struct {
+  int type;               /* enum kg_supervisor_layer_type */
+  size_t output_channels; /* Linear: >= 1 */
+  int function;           /* Activation: enum kg_supervisor_function */
+  float alpha, beta;      /* Activation */
+} kg_supervisor_layer;
+typedef struct {
+  size_t input_size, solution_size;                 /* Problem: Input / Size, Solution / Size */
+  size_t training_batch_size, inference_batch_size; /* Problem: the two batch sizes (>= 1) */
+  size_t layer_count;                               /* the hidden layers, the last Linear (solution_size
+                                                       channels) and the output activation, if any */
+  const kg_supervisor_layer *layers;
+  const float *output_scale, *output_shift; /* Output Layer: Scale, Shift (solution_size values, or NULL) */
+  const int *output_mask;                   /* Output Layer: Transformation Mask (enum kg_supervisor_mask, or NULL) */
+  int optimizer;                            /* enum kg_supervisor_optimizer */
+  int loss;                                 /* enum kg_supervisor_loss */
+  float learning_rate;
+  int l2_enabled;
+  float l2_importance; /* as the solver holds it (the generated parser truncates it to an integer) */
+  int device;
+} kg_supervisor_config;
+
+/* Limits, checked here with messages: every size >= 1, every layer width and
+ * batch size below 2^31, an Activation's width is its predecessor's, the last
+ * layer's width is solution_size. */
+int kg_supervisor_create(const kg_supervisor_config *cfg, kg_supervisor_t *out);
+int kg_supervisor_destroy(kg_supervisor_t h);
+int kg_supervisor_hyperparameter_count(kg_supervisor_t h, size_t *n);
+/* X: training_batch_size x input_size, S: training_batch_size x solution_size (host, row-major) */
+int kg_supervisor_set_training_data(kg_supervisor_t h, const float *X, const float *S);
+/* `steps` optimisation steps enqueued back to back; the loss (sum g^2 / (2 N),
+ * float, :132-136) of the last step is read once, after it.  Direct Gradient:
+ * the solution data are the output gradients of the last forward pass of
+ * training_batch_size rows (an error if there was none); *loss is left alone. */
+int kg_supervisor_train(kg_supervisor_t h, size_t steps, float *loss);
+/* rows must be one of the two batch sizes (neuralNetwork.cpp.base:344-360);
+ * out: rows x solution_size */
+int kg_supervisor_forward(kg_supervisor_t h, const float *X, size_t rows, float *out);
+/* backward of G (training_batch_size x solution_size) through the last forward
+ * pass of that size; fills the hyperparameter gradient, no optimizer step */
+int kg_supervisor_backward_direct(kg_supervisor_t h, const float *G);
+/* Fields (float): "hyperparameters", "gradient"; the optimizer's vectors
+ * ("first_moment", "second_moment" | "first_moment", "second_central_moment" |
+ * "s", "v", "z" | "r", "v" | "s"); "training_input", "training_solution";
+ * "output:<layer>" / "inference_output:<layer>" (a layer's values, batch x
+ * width; layer 0: the input of the last pass) and "output_gradient:<layer>"
+ * (the gradient with respect to a Linear layer's values).
+ * Scalars: "learning_rate", "current_loss", "beta1_pow", "beta2_pow",
+ * "model_evaluation_count" (settable); "layer_count", "tile", "k_step",
+ * "weight_gradient_splits:<layer>", "weight_gradient_chunk:<layer>". */
+int kg_supervisor_field_size(kg_supervisor_t h, const char *name, size_t *elem_bytes, size_t *count);
+int kg_supervisor_get_field(kg_supervisor_t h, const char *name, void *dst, size_t bytes);
+int kg_supervisor_set_field(kg_supervisor_t h, const char *name, const void *src, size_t bytes);
+int kg_supervisor_get_scalar(kg_supervisor_t h, const char *name, double *value);
+int kg_supervisor_set_scalar(kg_supervisor_t h, const char *name, double value);
+int kg_supervisor_synchronize(kg_supervisor_t h);
+/* Stage timers (HIP events; a profiled step waits for each stage): "forward",
+ * "data_gradient", "weight_gradient", "optimizer", "other".  profile_read
+ * returns and resets a stage's total. */
+int kg_supervisor_profile(kg_supervisor_t h, int enable);
+int kg_supervisor_profile_read(kg_supervisor_t h, const char *stage, double *ms_total, size_t *count);
 
 #ifdef __cplusplus
 }

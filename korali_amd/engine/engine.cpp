@@ -457,6 +457,10 @@ struct SolverModule {
   virtual std::string type() const = 0;
   // beside each result file, in its directory (VRACER: the training state)
   virtual void saveFiles(const std::string &dir) { (void)dir; }
+  // a Learner evaluates input batches (Experiment::getEvaluation); other solvers do not
+  virtual bool evaluate(const std::vector<std::vector<std::vector<float>>> &, std::vector<std::vector<float>> &) {
+    return false;
+  }
 };
 
 namespace {
@@ -2639,6 +2643,9 @@ bool dirExists(const std::string &p) {
 
 struct ExperimentState {
   std::unique_ptr<SolverModule> solver;
+  // a Learner outlives run() (the reference's _isInitialized): getEvaluation
+  // uses it, a further run continues with it
+  std::unique_ptr<SolverModule> learner;
   Logger log;
   // seconds from the start of the last run's loop until each generation's
   // termination check returned (generationCompletionTimes; kept out of the
@@ -2650,9 +2657,18 @@ std::vector<double> generationCompletionTimes(const Experiment &e) { return e._s
 
 Experiment::Experiment() : _state(new ExperimentState()) {}
 
-std::vector<std::vector<float>> Experiment::getEvaluation(const std::vector<std::vector<std::vector<float>>> &) {
-  // experiment.cpp.base:219-229: only a Learner solver evaluates input batches
-  fail("This solver does not support evaluation operations.\n");
+namespace {
+SolverModule *makeLearner(Json &js);
+}
+
+std::vector<std::vector<float>> Experiment::getEvaluation(const std::vector<std::vector<std::vector<float>>> &inputBatch) {
+  // experiment.cpp.base:219-229: an experiment not yet initialized is
+  // initialized first; only a Learner solver evaluates input batches
+  if (!_state->learner) _state->learner.reset(makeLearner(_js));
+  std::vector<std::vector<float>> out;
+  if (!_state->learner || !_state->learner->evaluate(inputBatch, out))
+    fail("This solver does not support evaluation operations.\n");
+  return out;
 }
 Experiment::~Experiment() = default;
 Experiment::Experiment(Experiment &&) noexcept = default;
@@ -3541,6 +3557,395 @@ struct DvracerModule : AgentModule {
   DvracerModule(Json &js, Seeder &seeds, bool resume) : AgentModule(js, seeds, resume, true) {}
 };
 
+// ------------------------------------------------------- DeepSupervisor
+// Learner / DeepSupervisor on a Supervised Learning problem
+// (deepSupervisor.cpp.base, supervisedLearning.cpp.base, neuralNetwork/layer/*)
+// on the device (kg_supervisor_*): feed-forward networks, one timestep.  The
+// configuration is parsed and checked on the host first; the device handle is
+// created when a run or an evaluation first needs it and then lives as long as
+// the experiment (the reference's _isInitialized: deepSupervisor.cpp.base:15),
+// so getEvaluation works after a run and a further run continues with the
+// same optimizer state.
+const KeyList LEARNER_KEYS = {"Neural Network", "Hyperparameters", "Loss Function", "Steps Per Generation", "Learning Rate",
+                              "L2 Regularization", "Output Weights Scaling", "Current Loss", "Normalization Means",
+                              "Normalization Variances"};
+const KeyList LEARNER_TERMINATION = {"Target Loss"};
+const KeyList SUPERVISED_KEYS = {"Type", "Training Batch Size", "Inference Batch Size", "Max Timesteps", "Input", "Solution"};
+
+void rejectKeys(const Json &mod, const char *moduleName, KeyList keys) {
+  if (!mod.is_object()) return;
+  Json left = Json::object();
+  for (const auto &kv : mod.items())
+    if (!inList(kv.first, {keys})) left[kv.first] = kv.second;
+  if (left.size()) fail(" + Unrecognized settings for Korali module: %s: \n%s\n", moduleName, left.dump(2).c_str());
+}
+
+struct DeepSupervisorModule : SolverModule {
+  kg_supervisor_t h = nullptr;
+  size_t N = 0, NI = 0, IC = 0, OC = 0;
+  std::vector<kg_supervisor_layer> layers;  // hidden layers, the last Linear, the output activation
+  std::vector<float> weightScaling;         // per entry of `layers` (Linear)
+  std::vector<float> scale, shift;
+  std::vector<int> mask;
+  int optimizer = 0, loss = 0;
+  bool l2 = false;
+  float l2Importance = 0.0f, learningRate = 0.0f, targetLoss = -1.0f, currentLoss = 0.0f;
+  size_t steps = 1, hyperparameterCount = 0;
+  double maxGenerations = 1e10, maxModelEvaluations = 1e10;
+  unsigned long long uniformSeed = 0;
+  std::vector<float> givenHyperparameters, X, S;
+
+  static size_t mandatoryCount(Json &j, const char *key, const char *shown, const char *module) {
+    if (!j.contains(key) || j[key].is_null())
+      fail(" + No value provided for mandatory setting: %s required by %s.\n", shown, module);
+    if (!j[key].is_number() || j[key].getDouble() < 0)
+      fail(" + Object: [ %s ] \n + Key:    %s\nthe value is not a non-negative integer\n", module, shown);
+    return (size_t)j[key].getUInt();
+  }
+
+  void readProblem(Json &js) {
+    if (!js.contains("Problem") || !js["Problem"].contains("Type")) fail("No problem type specified ('Problem' / 'Type').");
+    Json &pb = js["Problem"];
+    const std::string pt = canon(pb["Type"].getString());
+    if (pt != "supervisedlearning")
+      fail("Problems of type '%s' are not supported by the Learner/DeepSupervisor solver: it takes a 'Supervised Learning' "
+           "problem (hierarchical problems run under Sampler/TMCMC).", pb["Type"].getString().c_str());
+    rejectUnrecognised(pb, "supervisedLearning", {SUPERVISED_KEYS}, {});
+    rejectKeys(pb["Input"], "supervisedLearning", {"Data", "Size"});
+    rejectKeys(pb["Solution"], "supervisedLearning", {"Data", "Size"});
+    N = mandatoryCount(pb, "Training Batch Size", "['Training Batch Size']", "supervisedLearning");
+    NI = mandatoryCount(pb, "Inference Batch Size", "['Inference Batch Size']", "supervisedLearning");
+    const size_t T = (size_t)uint(pb, "Max Timesteps", 1);
+    IC = mandatoryCount(pb["Input"], "Size", "['Input']['Size']", "supervisedLearning");
+    OC = mandatoryCount(pb["Solution"], "Size", "['Solution']['Size']", "supervisedLearning");
+    // SupervisedLearning::initialize (supervisedLearning.cpp.base:8-11)
+    if (N == 0) fail("Empty input batch provided.\n");
+    if (T == 0) fail("Incorrect max timesteps provided: %lu.\n", (unsigned long)T);
+    if (IC == 0) fail("Empty input vector size provided.\n");
+    if (OC == 0) fail("Empty solution vector size provided.\n");
+    if (T != 1)
+      fail("'Max Timesteps' is %lu: recurrent networks are not provided by the device path; a Supervised Learning problem "
+           "takes one timestep (input data N x 1 x Input Size).\n", (unsigned long)T);
+    // NeuralNetwork::initialize (neuralNetwork.cpp.base:51-53)
+    if (NI == 0) fail("Batch size %lu is zero.\n", 1UL);
+  }
+
+  static int functionOf(const std::string &f, size_t index) {
+    static const std::pair<const char *, int> table[] = {
+        {"Elementwise/Tanh", KG_SV_TANH},         {"Elementwise/ReLU", KG_SV_RELU},
+        {"Elementwise/Logistic", KG_SV_LOGISTIC}, {"Elementwise/SoftReLU", KG_SV_SOFTRELU},
+        {"Elementwise/SoftSign", KG_SV_SOFTSIGN}, {"Elementwise/Linear", KG_SV_ELINEAR},
+        {"Elementwise/Log", KG_SV_LOG},           {"Softmax", KG_SV_SOFTMAX}};
+    for (const auto &t : table)
+      if (f == t.first) return t.second;
+    if (f == "Elementwise/Clip")
+      fail("Activation function 'Elementwise/Clip' (layer %lu) is not provided: the reference's Korali engine has no "
+           "backward branch for it (activation.cpp.base:270-314).\n", (unsigned long)index);
+    fail(" + Unrecognized value (%s) provided for mandatory setting: ['Function'] required by activation.\n", f.c_str());
+  }
+
+  void addActivation(const std::string &fn, float alpha, float beta, size_t index) {
+    kg_supervisor_layer l{};
+    l.type = KG_SV_ACTIVATION, l.function = functionOf(fn, index), l.alpha = alpha, l.beta = beta;
+    layers.push_back(l), weightScaling.push_back(1.0f);
+  }
+
+  void readSolver(Json &js, bool rerun) {
+    Json &sv = js["Solver"];
+    rejectUnrecognised(sv, "deepSupervisor", {SOLVER_KEYS, LEARNER_KEYS}, {SOLVER_TERMINATION, LEARNER_TERMINATION});
+    rejectKeys(sv["Neural Network"], "deepSupervisor", {"Hidden Layers", "Output Activation", "Output Layer", "Engine", "Optimizer"});
+    rejectKeys(sv["L2 Regularization"], "deepSupervisor", {"Enabled", "Importance"});
+    Json &nn = sv["Neural Network"];
+    if (!nn.contains("Hidden Layers") || nn["Hidden Layers"].is_null())
+      fail(" + No value provided for mandatory setting: ['Neural Network']['Hidden Layers'] required by deepSupervisor.\n");
+    const std::string outAct = str(nn, "Output Activation", "Identity");
+    if (!nn.contains("Output Layer") || nn["Output Layer"].is_null()) nn["Output Layer"] = Json::object();
+    if (!nn.contains("Engine") || !nn["Engine"].is_string())
+      fail(" + No value provided for mandatory setting: ['Neural Network']['Engine'] required by deepSupervisor.\n");
+    const std::string engine = nn["Engine"].getString();
+    if (engine != "Korali" && engine != "OneDNN" && engine != "CuDNN")
+      fail("Neural Network Engine '%s' is not recognized: 'Korali', 'OneDNN' and 'CuDNN' all select the device.\n", engine.c_str());
+    if (!nn.contains("Optimizer") || !nn["Optimizer"].is_string())
+      fail(" + No value provided for mandatory setting: ['Neural Network']['Optimizer'] required by deepSupervisor.\n");
+    const std::string opt = nn["Optimizer"].getString();
+    static const char *optimizers[] = {"Adam", "AdaBelief", "MADGRAD", "RMSProp", "Adagrad"};
+    optimizer = -1;
+    for (int i = 0; i < 5; i++)
+      if (opt == optimizers[i]) optimizer = i;
+    if (optimizer < 0)
+      fail(" + Unrecognized value (%s) provided for mandatory setting: ['Neural Network']['Optimizer'] required by "
+           "deepSupervisor.\n", opt.c_str());
+    if (!sv.contains("Loss Function") || !sv["Loss Function"].is_string())
+      fail(" + No value provided for mandatory setting: ['Loss Function'] required by deepSupervisor.\n");
+    const std::string lf = sv["Loss Function"].getString();
+    if (lf == "Mean Squared Error") loss = KG_SV_MEAN_SQUARED_ERROR;
+    else if (lf == "Direct Gradient") loss = KG_SV_DIRECT_GRADIENT;
+    else fail(" + Unrecognized value (%s) provided for mandatory setting: ['Loss Function'] required by deepSupervisor.\n", lf.c_str());
+    steps = (size_t)uint(sv, "Steps Per Generation", 1);
+    if (!sv.contains("Learning Rate") || !sv["Learning Rate"].is_number())
+      fail(" + No value provided for mandatory setting: ['Learning Rate'] required by deepSupervisor.\n");
+    learningRate = (float)sv["Learning Rate"].getDouble();
+    l2 = flag(sv["L2 Regularization"], "Enabled", false);
+    // the generated parser reads the importance through get<int>(): 0.05 acts as 0
+    l2Importance = (float)(int)num(sv["L2 Regularization"], "Importance", 1e-4);
+    const float ows = (float)num(sv, "Output Weights Scaling", 1.0);
+    Json &tc = sv["Termination Criteria"];
+    targetLoss = (float)num(tc, "Target Loss", -1.0);
+    maxGenerations = num(tc, "Max Generations", 1e10);
+    maxModelEvaluations = num(tc, "Max Model Evaluations", 1e10);
+    if (!sv.contains("Hyperparameters") || sv["Hyperparameters"].is_null()) sv["Hyperparameters"] = std::vector<float>();
+    currentLoss = (float)num(sv, "Current Loss", 0.0);
+    if (rerun) return;  // the network itself stays as the first run built it (deepSupervisor.cpp.base:15)
+    // the layers (deepSupervisor.cpp.base:27-59)
+    layers.clear(), weightScaling.clear();
+    const Json &hl = nn["Hidden Layers"];
+    if (!hl.is_array()) fail(" + Object: [ deepSupervisor ] \n + Key:    ['Neural Network']['Hidden Layers']\nnot an array\n");
+    size_t width = IC;
+    for (size_t i = 0; i < hl.size(); i++) {
+      Json ly = hl.at(i);
+      const size_t index = i + 1;
+      if (!ly.contains("Type") || !ly["Type"].is_string()) fail("Hidden layer %lu has no 'Type'.\n", (unsigned long)index);
+      const std::string shown = ly["Type"].getString(), t = canon(shown);
+      if (t == "layer/linear") {
+        rejectKeys(ly, "linear", {"Type", "Output Channels", "Weight Scaling"});
+        kg_supervisor_layer l{};
+        l.type = KG_SV_LINEAR, l.output_channels = (size_t)uint(ly, "Output Channels", 0);
+        // linear.cpp.base:21
+        if (l.output_channels == 0) fail("Node count for layer (%lu) should be larger than zero.\n", (unsigned long)index);
+        layers.push_back(l);
+        // :38-39: the Output Weights Scaling written first is overwritten by the layer's own setting
+        weightScaling.push_back((float)num(ly, "Weight Scaling", 1.0));
+        width = l.output_channels;
+      } else if (t == "layer/activation") {
+        rejectKeys(ly, "activation", {"Type", "Function", "Alpha", "Beta", "Output Channels", "Weight Scaling"});
+        if (!ly.contains("Function") || !ly["Function"].is_string())
+          fail(" + No value provided for mandatory setting: ['Function'] required by activation.\n");
+        const size_t oc = (size_t)uint(ly, "Output Channels", 0);
+        // activation.cpp.base: an activation keeps its predecessor's width
+        if (oc != 0 && oc != width)
+          fail("Activation layer %lu: 'Output Channels' (%lu) differs from the previous layer's (%lu).\n", (unsigned long)index,
+               (unsigned long)oc, (unsigned long)width);
+        addActivation(ly["Function"].getString(), (float)num(ly, "Alpha", 1.0), (float)num(ly, "Beta", 0.0), index);
+      } else if (t == "layer/convolution" || t == "layer/deconvolution" || t == "layer/pooling" || t.rfind("layer/recurrent", 0) == 0) {
+        fail("Layer type '%s' (hidden layer %lu) is not provided by the device path: it runs feed-forward networks of "
+             "'Layer/Linear' and 'Layer/Activation'.\n", shown.c_str(), (unsigned long)index);
+      } else {
+        fail("Unrecognized layer type '%s' (hidden layer %lu).\n", shown.c_str(), (unsigned long)index);
+      }
+    }
+    kg_supervisor_layer last{};
+    last.type = KG_SV_LINEAR, last.output_channels = OC;
+    layers.push_back(last), weightScaling.push_back(ows);
+    if (outAct != "Identity") addActivation(outAct, 1.0f, 0.0f, layers.size() + 1);
+    // the Output layer (output.cpp.base:29-82)
+    Json &ol = nn["Output Layer"];
+    rejectKeys(ol, "output", {"Type", "Scale", "Shift", "Transformation Mask", "Output Channels", "Weight Scaling"});
+    scale.clear(), shift.clear(), mask.clear();
+    if (ol.contains("Scale") && ol["Scale"].is_array()) scale = ol["Scale"].get<std::vector<float>>();
+    if (ol.contains("Shift") && ol["Shift"].is_array()) shift = ol["Shift"].get<std::vector<float>>();
+    if (!scale.empty() && scale.size() != OC)
+      fail("Wrong number of output scaling factors passed to the neural network. Expected: %lu, provided: %lu.\n",
+           (unsigned long)OC, (unsigned long)scale.size());
+    if (!shift.empty() && shift.size() != OC)
+      fail("Wrong number of output shift factors passed to the neural network. Expected: %lu, provided: %lu.\n",
+           (unsigned long)OC, (unsigned long)shift.size());
+    if (ol.contains("Transformation Mask") && ol["Transformation Mask"].is_array() && ol["Transformation Mask"].size() > 0) {
+      const Json &tm = ol["Transformation Mask"];
+      if (tm.size() != OC)
+        fail("Wrong size of transformation mask specified: %lu, expected: %lu.\n", (unsigned long)tm.size(), (unsigned long)OC);
+      static const char *masks[] = {"Identity", "Absolute", "Softplus", "Tanh", "Sigmoid"};
+      for (size_t i = 0; i < OC; i++) {
+        const std::string m = tm.at(i).is_string() ? tm.at(i).getString() : std::string("?");
+        int code = -1;
+        for (int c = 0; c < 5; c++)
+          if (m == masks[c]) code = c;
+        if (code < 0) fail("Wrong transformation mask specified: %s for output variable %lu.\n", m.c_str(), (unsigned long)i);
+        mask.push_back(code);
+      }
+    }
+    hyperparameterCount = 0;
+    width = IC;
+    for (const auto &l : layers)
+      if (l.type == KG_SV_LINEAR) hyperparameterCount += width * l.output_channels + l.output_channels, width = l.output_channels;
+    givenHyperparameters = sv["Hyperparameters"].get<std::vector<float>>();
+    if (!givenHyperparameters.empty() && givenHyperparameters.size() != hyperparameterCount)
+      fail("'Hyperparameters' holds %lu values; the network has %lu.\n", (unsigned long)givenHyperparameters.size(),
+           (unsigned long)hyperparameterCount);
+  }
+
+  // SupervisedLearning::verifyData (supervisedLearning.cpp.base:18-48) while flattening
+  void readData(Json &js) {
+    const Json &pb = js["Problem"];
+    static const Json empty = Json::array();
+    const Json &in = pb.at("Input").contains("Data") ? pb.at("Input").at("Data") : empty;
+    const Json &so = pb.at("Solution").contains("Data") ? pb.at("Solution").at("Data") : empty;
+    if (!in.is_array() || in.size() == 0) fail("Empty input dataset provided.\n");
+    if (!so.is_array() || so.size() == 0) fail("Empty solution dataset provided.\n");
+    if (N != in.size())
+      fail("Training Batch size %lu  different than that of input data (%lu).\n", (unsigned long)in.size(), (unsigned long)N);
+    X.assign(N * IC, 0.0f), S.assign(N * OC, 0.0f);
+    for (size_t b = 0; b < N; b++) {
+      const Json &e = in.at(b);
+      const size_t ts = e.is_array() ? e.size() : 0;
+      if (ts > 1)
+        fail("More timesteps (%lu) provided in batch %lu than max specified in the configuration (%lu).\n", (unsigned long)ts,
+             (unsigned long)b, 1UL);
+      if (ts == 0)
+        fail("Input data entry %lu holds no timestep: the data are N x 1 x Input Size (recurrent networks, with their "
+             "variable sequence lengths, are not provided).\n", (unsigned long)b);
+      const std::vector<double> v = e.at(0).is_array() ? e.at(0).getDoubleVector() : std::vector<double>();
+      if (v.size() != IC)
+        fail("Vector size of timestep %lu input data %lu is inconsistent. Size: %lu - Expected: %lu.\n", (unsigned long)b, 0UL,
+             (unsigned long)v.size(), (unsigned long)IC);
+      for (size_t i = 0; i < IC; i++) X[b * IC + i] = (float)v[i];
+    }
+    if (N != so.size())
+      fail("Training Batch size of solution data (%lu) is different than that of input data (%lu).\n", (unsigned long)so.size(),
+           (unsigned long)in.size());
+    for (size_t b = 0; b < N; b++) {
+      const std::vector<double> v = so.at(b).is_array() ? so.at(b).getDoubleVector() : std::vector<double>();
+      if (v.size() != OC)
+        fail("Solution vector size of batch %lu is inconsistent. Size: %lu - Expected: %lu.\n", (unsigned long)b,
+             (unsigned long)v.size(), (unsigned long)OC);
+      for (size_t i = 0; i < OC; i++) S[b * OC + i] = (float)v[i];
+    }
+  }
+
+  // linear.cpp.base:28-49 with the network's Univariate/Uniform(-1, 1)
+  // generator: gsl_ran_flat on GSL's mt19937 (std::mt19937 has its seeding
+  // and its output; GSL maps the seed 0 to 4357)
+  std::vector<float> initialHyperparameters() const {
+    std::mt19937 mt(uniformSeed == 0 ? 4357u : (unsigned)uniformSeed);
+    std::vector<float> theta;
+    theta.reserve(hyperparameterCount);
+    size_t ic = IC;
+    for (size_t i = 0; i < layers.size(); i++) {
+      if (layers[i].type != KG_SV_LINEAR) continue;
+      const size_t oc = layers[i].output_channels;
+      // :36: a float numerator over the double square root of a size_t, the double quotient rounded once
+      const float xavier = (float)((double)std::sqrt(6.0f) / std::sqrt((double)(oc + ic)));
+      const float scaled = weightScaling[i] * xavier;
+      for (size_t k = 0; k < oc * ic; k++) {
+        const double u = mt() / 4294967296.0;
+        theta.push_back((float)(scaled * (-1.0 * (1.0 - u) + 1.0 * u)));
+      }
+      for (size_t k = 0; k < oc; k++) theta.push_back(0.0f);
+      ic = oc;
+    }
+    return theta;
+  }
+
+  DeepSupervisorModule(Json &js, Seeder &seeds) {
+    readProblem(js);
+    readSolver(js, false);
+    uniformSeed = seeds.counter++;  // the network's generator, as AgentModule seeds its own
+  }
+
+  ~DeepSupervisorModule() override {
+    if (h) kg_supervisor_destroy(h);
+  }
+
+  void ensureDevice() {
+    if (h) return;
+    kg_supervisor_config c{};
+    c.input_size = IC, c.solution_size = OC, c.training_batch_size = N, c.inference_batch_size = NI;
+    c.layer_count = layers.size(), c.layers = layers.data();
+    c.output_scale = scale.empty() ? nullptr : scale.data();
+    c.output_shift = shift.empty() ? nullptr : shift.data();
+    c.output_mask = mask.empty() ? nullptr : mask.data();
+    c.optimizer = optimizer, c.loss = loss, c.learning_rate = learningRate;
+    c.l2_enabled = l2 ? 1 : 0, c.l2_importance = l2Importance, c.device = 0;
+    check(kg_supervisor_create(&c, &h));
+    size_t n = 0;
+    check(kg_supervisor_hyperparameter_count(h, &n));
+    if (n != hyperparameterCount)
+      fail("Learner/DeepSupervisor: hyperparameter count mismatch (%zu vs the device's %zu).", hyperparameterCount, n);
+    const std::vector<float> theta = givenHyperparameters.empty() ? initialHyperparameters() : givenHyperparameters;
+    check(kg_supervisor_set_field(h, "hyperparameters", theta.data(), n * sizeof(float)));
+  }
+
+  // before each run: the settings a run re-reads, the problem's data
+  void prepareRun(Json &js, bool rerun) {
+    if (rerun) {
+      const size_t n0 = N, ni0 = NI, ic0 = IC, oc0 = OC;
+      readProblem(js);
+      const bool changed = N != n0 || NI != ni0 || IC != ic0 || OC != oc0;
+      N = n0, NI = ni0, IC = ic0, OC = oc0;
+      if (changed)
+        fail("The batch and vector sizes of the problem changed between runs of one experiment; the network was built "
+             "for the first run's.\n");
+      readSolver(js, true);
+    }
+    readData(js);
+    ensureDevice();
+    check(kg_supervisor_set_training_data(h, X.data(), S.data()));
+  }
+
+  void runGeneration(size_t) override {
+    // deepSupervisor.cpp.base:104: the learning rate is re-read every generation
+    check(kg_supervisor_set_scalar(h, "learning_rate", learningRate));
+    float l = currentLoss;
+    check(kg_supervisor_train(h, steps, &l));
+    currentLoss = l;
+  }
+
+  void checkTermination(size_t gen, std::vector<std::string> &met) override {
+    if ((double)gen > maxGenerations) met.push_back("Max Generations");
+    if (maxModelEvaluations <= 0.0) met.push_back("Max Model Evaluations");  // (the learner counts none)
+    // deepSupervisor.config:96
+    if (gen > 1 && targetLoss > 0.0f && currentLoss <= targetLoss) met.push_back("Target Loss");
+  }
+
+  std::vector<float> hyperparameters() {
+    std::vector<float> theta(hyperparameterCount);
+    check(kg_supervisor_get_field(h, "hyperparameters", theta.data(), theta.size() * sizeof(float)));
+    return theta;
+  }
+
+  void getConfiguration(Json &sv) override {
+    // no optimizer state: a run resumed from a result file starts a fresh optimizer, as the reference's does
+    sv["Hyperparameters"] = hyperparameters();
+    sv["Current Loss"] = (double)currentLoss;
+    sv["Normalization Means"] = std::vector<float>();
+    sv["Normalization Variances"] = std::vector<float>();
+    sv["Model Evaluation Count"] = 0ULL;
+  }
+
+  void finalize(Json &) override {}
+
+  void printAfter(const Logger &log) override {
+    // deepSupervisor.cpp.base:201-206
+    if (loss == KG_SV_MEAN_SQUARED_ERROR) log.log(2, " + Training Loss: %.15f\n", (double)currentLoss);
+    if (loss == KG_SV_DIRECT_GRADIENT) log.log(2, " + Gradient L2-Norm: %.15f\n", (double)std::sqrt(currentLoss));
+  }
+
+  std::string type() const override { return "Learner/DeepSupervisor"; }
+
+  // DeepSupervisor::getEvaluation (:177-187)
+  bool evaluate(const std::vector<std::vector<std::vector<float>>> &input, std::vector<std::vector<float>> &out) override {
+    const size_t rows = input.size();
+    // NeuralNetwork::getBatchSizeIdx (neuralNetwork.cpp.base:344-360)
+    if (rows != N && rows != NI)
+      fail("Batch size (%lu) of input is not within the configured batch sizes of the neural network..\n", (unsigned long)rows);
+    std::vector<float> x(rows * IC);
+    for (size_t b = 0; b < rows; b++) {
+      if (input[b].size() != 1)
+        fail("Input entry %lu holds %lu timesteps: the device path evaluates one timestep per entry (recurrent networks are "
+             "not provided).\n", (unsigned long)b, (unsigned long)input[b].size());
+      if (input[b][0].size() != IC)
+        fail("Vector size of timestep %lu input data %lu is inconsistent. Size: %lu - Expected: %lu.\n", (unsigned long)b, 0UL,
+             (unsigned long)input[b][0].size(), (unsigned long)IC);
+      std::copy(input[b][0].begin(), input[b][0].end(), x.begin() + b * IC);
+    }
+    ensureDevice();
+    std::vector<float> y(rows * OC);
+    check(kg_supervisor_forward(h, x.data(), rows, y.data()));
+    out.assign(rows, std::vector<float>(OC));
+    for (size_t b = 0; b < rows; b++) std::copy(y.begin() + b * OC, y.begin() + (b + 1) * OC, out[b].begin());
+    return true;
+  }
+};
+
 // KORALI_AMD_RUN_PHASES=1: the wall time of each phase of a run on stderr
 // (the engine's fixed cost outside the generation loop)
 struct PhaseClock {
@@ -3632,8 +4037,13 @@ void runExperiment(Experiment &e, Conduit &conduit) {
   // Python binding) has the GIL released
   struct SolverRelease {
     ExperimentState &st;
-    ~SolverRelease() { st.solver.reset(); }
+    bool keep = false;  // a Learner goes back to the experiment
+    ~SolverRelease() {
+      if (keep && st.solver) st.learner = std::move(st.solver);
+      st.solver.reset();
+    }
   } release{st};
+  if (stype != "learner/deepsupervisor" && stype != "deepsupervisor") st.learner.reset();
   if (stype == "optimizer/cmaes" || stype == "cmaes") {
     st.solver.reset(new CmaesModule(js, seeds, resume, dist));
   } else if (stype == "optimizer/mocmaes" || stype == "mocmaes") {
@@ -3655,9 +4065,20 @@ void runExperiment(Experiment &e, Conduit &conduit) {
       fail("Agent/Discrete/dVRACER does not shard across ranks: run one experiment per GPU with the Sequential "
            "conduit (independent replicas).");
     st.solver.reset(new DvracerModule(js, seeds, resume));
+  } else if (stype == "learner/deepsupervisor" || stype == "deepsupervisor") {
+    if (dist)
+      fail("Learner/DeepSupervisor does not shard across ranks: run one experiment per GPU with the Sequential conduit.");
+    // a new learner belongs to the experiment only once its first run is prepared: a configuration
+    // or data error leaves nothing behind, and the corrected experiment starts afresh
+    const bool rerun = (bool)st.learner;
+    std::unique_ptr<SolverModule> fresh;
+    if (!rerun) fresh.reset(new DeepSupervisorModule(js, seeds));
+    static_cast<DeepSupervisorModule *>(rerun ? st.learner.get() : fresh.get())->prepareRun(js, rerun);
+    st.solver = rerun ? std::move(st.learner) : std::move(fresh);
+    release.keep = true;
   } else {
     fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Optimizer/MOCMAES, Sampler/TMCMC, "
-         "Sampler/Nested, Agent/Continuous/VRACER and Agent/Discrete/dVRACER).",
+         "Sampler/Nested, Agent/Continuous/VRACER, Agent/Discrete/dVRACER and Learner/DeepSupervisor).",
          sv["Type"].getString().c_str());
   }
   clk.mark("setup");
@@ -3725,8 +4146,33 @@ void runExperiment(Experiment &e, Conduit &conduit) {
   for (const auto &m : met) st.log.log(2, "Termination Criterion Met: %s\n", m.c_str());
   st.log.log(2, "Final Generation: %zu\n", gen);
   st.log.log(2, "Elapsed Time: %.3fs\n", std::chrono::duration<double>(t1 - t0).count());
+  if (release.keep) st.learner = std::move(st.solver);
   st.solver.reset();  // release the device handle
   clk.mark("release");
+}
+
+// Experiment::getEvaluation on an experiment that has not run: the learner
+// from its configuration (nullptr: the solver is absent or no learner)
+SolverModule *makeLearner(Json &js) {
+  const Json &cjs = js;
+  const Json *sv = cjs.contains("Solver") ? &cjs.at("Solver") : nullptr;
+  const Json *ty = sv && sv->is_object() ? member(*sv, "Type") : nullptr;
+  if (!ty || !ty->is_string()) return nullptr;
+  const std::string stype = canon(ty->getString());
+  if (stype != "learner/deepsupervisor" && stype != "deepsupervisor") return nullptr;
+  // Experiment::setSeed: 0 -> time
+  if (num(js, "Random Seed", 0) == 0)
+    js["Random Seed"] = (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(
+                            std::chrono::high_resolution_clock::now().time_since_epoch())
+                            .count();
+  // the distributions take their seeds first, as in a run (experiment.cpp:255-340): the network's
+  // generator gets the same seed whether an evaluation or a run comes first
+  Seeder seeds{js["Random Seed"].getUInt(), flag(js, "Preserve Random Number Generator States", false)};
+  if (js.contains("Distributions") && js["Distributions"].is_array())
+    for (size_t d = 0; d < js["Distributions"].size(); d++) seeds.assign(js["Distributions"][d]);
+  SolverModule *m = new DeepSupervisorModule(js, seeds);
+  js["Random Seed"] = seeds.counter;
+  return m;
 }
 
 }  // namespace

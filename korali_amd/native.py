@@ -161,6 +161,11 @@ EXPORTED = [
     "kg_nested_process", "kg_nested_finalize", "kg_nested_field_size", "kg_nested_get_field", "kg_nested_set_field",
     "kg_nested_get_rng", "kg_nested_set_rng", "kg_nested_diagnostics", "kg_nested_profile",
     "kg_nested_profile_read", "kg_nested_synchronize", "kg_nested_permutation",
+    "kg_supervisor_create", "kg_supervisor_destroy", "kg_supervisor_hyperparameter_count",
+    "kg_supervisor_set_training_data", "kg_supervisor_train", "kg_supervisor_forward",
+    "kg_supervisor_backward_direct", "kg_supervisor_field_size", "kg_supervisor_get_field",
+    "kg_supervisor_set_field", "kg_supervisor_get_scalar", "kg_supervisor_set_scalar",
+    "kg_supervisor_synchronize", "kg_supervisor_profile", "kg_supervisor_profile_read",
     "kg_tmcmc_create", "kg_tmcmc_destroy", "kg_tmcmc_generation", "kg_tmcmc_synchronize", "kg_tmcmc_field_size",
     "kg_tmcmc_get_field", "kg_tmcmc_set_field", "kg_tmcmc_get_rng", "kg_tmcmc_set_rng", "kg_tmcmc_prepare",
     "kg_tmcmc_evaluate", "kg_tmcmc_process", "kg_tmcmc_advance", "kg_tmcmc_get_pending",

@@ -474,6 +474,54 @@ int kg_mocmaes_profile_read(kg_mocmaes_t h, const char *stage, double *ms_total,
  * (window624 = 624 consecutive untempered words of a GSL mt19937 stream,
  * not starting at the seeding word 0).  Runs on the host, no device needed. */
 int kg_debug_mt_jump(const uint32_t *window624, uint64_t distance, uint32_t *out624);
+/* One device mt19937 stream (csrc/kg_rng.hpp MtStream: the generator every
+ * solver draws its normals and uniforms from) with no solver around it.  Each
+ * entry is the MtStream call of its name on the handle's stream, waited for;
+ * host arrays travel through device buffers the handle owns.
+ * open: a ring for capacity_words beyond the current block on `device`, then
+ * the import of a 5000-byte GSL state (nonzero return for an mti outside
+ * [0, 624]).  KORALI_AMD_MT_PARALLEL_MIN / _CHUNK_LOG2 / _CHUNK_PARTS choose
+ * the producer as they do for the solvers.  import: the same import again on
+ * the used handle. */
+typedef struct kg_debug_mt_s *kg_debug_mt_t;
+int kg_debug_mt_open(int device, size_t capacity_words, const void *state5000, kg_debug_mt_t *out);
+int kg_debug_mt_close(kg_debug_mt_t h);
+int kg_debug_mt_import(kg_debug_mt_t h, const void *state5000);
+/* the polar count and scatter passes' workgroups for a draw of M normals */
+int kg_debug_mt_count_blocks(kg_debug_mt_t h, size_t M, size_t *count_blocks);
+/* M gsl_ran_gaussian(1) normals, not consumed: normal k of [k_lo, min(k_hi, M))
+ * into z[k - k_lo]; z (z_len doubles, at least the window) is uploaded first
+ * and read back whole, so entries the pass does not write keep the caller's
+ * values.  block_end (NULL, or M / block_len entries, uploaded and read back
+ * the same way): the attempt index of normal (b+1) block_len - 1; it stays
+ * on the device for the consume entries.  *count_blocks (may be NULL) as
+ * kg_debug_mt_count_blocks, the grid this draw launched. */
+int kg_debug_mt_polar_normals(kg_debug_mt_t h, size_t M, size_t block_len, size_t k_lo, size_t k_hi, double *z,
+                              size_t z_len, unsigned long long *block_end, size_t *count_blocks);
+/* Advance past `used` normals of the last draw: through its block_end
+ * (use_block_end, `used` a multiple of that draw's block_len) or through the
+ * draw's own record of normal M - 1 (used == M).  _dev: used_blocks blocks of
+ * block_len normals, the count read from device memory. */
+int kg_debug_mt_consume_normals(kg_debug_mt_t h, size_t used, size_t block_len, int use_block_end);
+int kg_debug_mt_consume_normals_dev(kg_debug_mt_t h, unsigned long long used_blocks, size_t block_len);
+/* M gsl_rng_uniform draws, consumed (uniforms) or not (peek_uniforms), and the
+ * consumption of `words` words, the count read from device memory. */
+int kg_debug_mt_uniforms(kg_debug_mt_t h, size_t M, double *u);
+int kg_debug_mt_peek_uniforms(kg_debug_mt_t h, size_t M, double *u);
+int kg_debug_mt_consume_words_dev(kg_debug_mt_t h, unsigned long long words);
+/* The side stream: the producer for M normals (prefetch); the polar pass on
+ * it into the handle's buffer, uploaded from z (z_len >= M) first, *launched
+ * = 0 when no side stream exists yet (polar_normals_ahead); join, then the
+ * buffer's first z_len doubles into z (NULL: the join alone). */
+int kg_debug_mt_prefetch(kg_debug_mt_t h, size_t M);
+int kg_debug_mt_polar_normals_ahead(kg_debug_mt_t h, size_t M, size_t block_len, const double *z, size_t z_len,
+                                    int *launched);
+int kg_debug_mt_join(kg_debug_mt_t h, double *z, size_t z_len);
+int kg_debug_mt_export_gsl(kg_debug_mt_t h, void *state5000);
+/* The device's StreamState: out7 = lo, pos, hi, nzero, errors (KG_ERR_* bits:
+ * 2 generator underrun, 8 zero-word list full), last_attempt, total_normals;
+ * *ring_words (may be NULL) the ring's size in words. */
+int kg_debug_mt_state(kg_debug_mt_t h, unsigned long long *out7, unsigned long long *ring_words);
 /* The host core's tridiagonalisation (phase A of CMAES::eigen,
  * CMAES.cpp.base:896-938 → gsl_linalg_symmtd_decomp, run every generation
  * from prepareGeneration :441) on a given matrix: C row-major N x N (lower

@@ -550,13 +550,22 @@ int MtStream::import_gsl(const void *state5000, hipStream_t s) {
   int32_t mti;
   memcpy(&mti, b + 8 * MT_N, 4);
   KG_CHECK(mti >= 0 && mti <= MT_N, "invalid mt19937 state (mti out of range)");
+  if (prefetch_pending_) {  // a producer still queued on the side stream would extend the replaced state
+    KG_HIP(hipStreamWaitEvent(s, ev_side_, 0));
+    prefetch_pending_ = false;
+  }
   StreamState h;
   memset(&h, 0, sizeof(h));
   h.lo = 0;
   h.pos = (unsigned long long)mti;
   h.hi = MT_N;
   for (int i = mti; i < MT_N; i++)
-    if (w[i] == 0 && h.nzero < KG_MAX_ZERO_WORDS) h.zeros[h.nzero++] = (unsigned long long)i;
+    if (w[i] == 0) {
+      if (h.nzero < KG_MAX_ZERO_WORDS)
+        h.zeros[h.nzero++] = (unsigned long long)i;
+      else
+        h.errors |= KG_ERR_ZERO_LIST;
+    }
   KG_HIP(hipMemcpyAsync(ring_, w.data(), MT_N * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   KG_HIP(hipMemcpyAsync(st_, &h, sizeof(h), hipMemcpyHostToDevice, s));
   if (par_ && seed_chunks(h.pos, s)) return 1;
@@ -645,6 +654,11 @@ size_t MtStream::words_for_normals(size_t M) const {
   return (size_t)(2.0 * A) + 64;
 }
 
+size_t MtStream::count_blocks(size_t M) const {
+  const unsigned long long A = words_for_normals(M) / 2;
+  return (size_t)((A + POLAR_APB - 1) / POLAR_APB);
+}
+
 int MtStream::prefetch(size_t M, hipStream_t main) {
   if (!side_) {
     KG_HIP(stream_acquire(&side_));
@@ -682,7 +696,7 @@ int MtStream::polar_normals(double *z, size_t M, size_t block_len, unsigned long
                             size_t k_lo, size_t k_hi) {
   const unsigned long long words = words_for_normals(M);
   const unsigned long long A = words / 2;
-  const size_t nb = (size_t)((A + POLAR_APB - 1) / POLAR_APB);
+  const size_t nb = count_blocks(M);
   if (ensure_scratch(nb)) return 1;
   if (prefetch_pending_) {
     KG_HIP(hipStreamWaitEvent(s, ev_side_, 0));
@@ -742,3 +756,219 @@ int MtStream::consume_words_dev(const unsigned long long *words, hipStream_t s) 
 }
 
 }  // namespace kg
+
+// ---- testing: one MtStream with no solver around it (include/korali_amd.h
+// "testing", tests/test_gpu_mt_stream.py).  Every entry is the MtStream call
+// of its name on the handle's stream, then a wait; the checks are on what
+// the host hands in (buffer lengths, block counts), never on the stream.
+struct kg_debug_mt_s {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  kg::MtStream mt;
+  double *z = nullptr;  // normals / uniforms
+  size_t zcap = 0;
+  unsigned long long *blockEnd = nullptr;
+  size_t becap = 0, beCount = 0, beLen = 0;  // the last draw's block_end entries and block_len
+  unsigned long long *count = nullptr;       // the count a consume kernel reads from device memory
+};
+
+namespace {
+
+template <class T>
+int debug_mt_grow(T **p, size_t *cap, size_t n) {
+  if (n == 0) n = 1;
+  if (n <= *cap) return 0;
+  if (*p) {
+    KG_HIP(hipDeviceSynchronize());
+    kg::dev_release(*p);
+    *p = nullptr;
+    *cap = 0;
+  }
+  KG_HIP(kg::dev_alloc(p, n * sizeof(T)));
+  *cap = n;
+  return 0;
+}
+
+int debug_mt_count(kg_debug_mt_s *h, unsigned long long v) {
+  KG_HIP(hipMemcpyAsync(h->count, &v, sizeof(v), hipMemcpyHostToDevice, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+constexpr size_t DEBUG_MT_MAX = (size_t)1 << 24;
+
+}  // namespace
+
+extern "C" int kg_debug_mt_close(kg_debug_mt_t h) {
+  if (!h) return 0;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  h->mt.drain();
+  if (h->z) kg::dev_release(h->z);
+  if (h->blockEnd) kg::dev_release(h->blockEnd);
+  if (h->count) kg::dev_release(h->count);
+  hipStream_t s = h->stream;
+  delete h;  // (the stream outlives the MtStream that waited on it)
+  if (s) kg::stream_release(s);
+  return 0;
+}
+
+extern "C" int kg_debug_mt_open(int device, size_t capacity_words, const void *state5000, kg_debug_mt_t *out) {
+  KG_CHECK(state5000 && out, "kg_debug_mt_open: null argument");
+  KG_CHECK(capacity_words >= 1 && capacity_words <= ((size_t)1 << 28), "kg_debug_mt_open: 1 <= capacity_words <= 2^28");
+  KG_HIP(hipSetDevice(device));
+  kg::upload_dd_tables();  // log_cr of the polar normals
+  auto *h = new kg_debug_mt_s();
+  h->device = device;
+  if (kg::stream_acquire(&h->stream) != hipSuccess || kg::dev_alloc(&h->count, sizeof(unsigned long long)) != hipSuccess) {
+    kg::set_error("kg_debug_mt_open: device allocation failed");
+    kg_debug_mt_close(h);
+    return 1;
+  }
+  if (h->mt.init(capacity_words) || h->mt.import_gsl(state5000, h->stream)) {
+    kg_debug_mt_close(h);
+    return 1;
+  }
+  *out = h;
+  return 0;
+}
+
+extern "C" int kg_debug_mt_import(kg_debug_mt_t h, const void *state5000) {
+  KG_CHECK(h && state5000, "kg_debug_mt_import: null argument");
+  KG_HIP(hipSetDevice(h->device));
+  return h->mt.import_gsl(state5000, h->stream);
+}
+
+extern "C" int kg_debug_mt_count_blocks(kg_debug_mt_t h, size_t M, size_t *count_blocks) {
+  KG_CHECK(h && count_blocks, "kg_debug_mt_count_blocks: null argument");
+  *count_blocks = h->mt.count_blocks(M);
+  return 0;
+}
+
+extern "C" int kg_debug_mt_polar_normals(kg_debug_mt_t h, size_t M, size_t block_len, size_t k_lo, size_t k_hi,
+                                         double *z, size_t z_len, unsigned long long *block_end,
+                                         size_t *count_blocks) {
+  KG_CHECK(h && z, "kg_debug_mt_polar_normals: null argument");
+  KG_CHECK(M >= 1 && M <= DEBUG_MT_MAX && z_len <= DEBUG_MT_MAX, "kg_debug_mt_polar_normals: 1 <= M, z_len <= 2^24");
+  const size_t hi = k_hi < M ? k_hi : M;
+  KG_CHECK(k_lo >= hi || hi - k_lo <= z_len, "kg_debug_mt_polar_normals: z is shorter than the window");
+  KG_CHECK(!block_end || block_len >= 1, "kg_debug_mt_polar_normals: block_end needs a block_len");
+  KG_HIP(hipSetDevice(h->device));
+  const size_t nbe = block_end ? M / block_len : 0;
+  if (debug_mt_grow(&h->z, &h->zcap, z_len) || debug_mt_grow(&h->blockEnd, &h->becap, nbe)) return 1;
+  KG_HIP(hipMemcpyAsync(h->z, z, z_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (nbe) KG_HIP(hipMemcpyAsync(h->blockEnd, block_end, nbe * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  h->beCount = 0;
+  if (h->mt.polar_normals(h->z, M, block_len, block_end ? h->blockEnd : nullptr, h->stream, k_lo, k_hi)) return 1;
+  KG_HIP(hipMemcpyAsync(z, h->z, z_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (nbe) KG_HIP(hipMemcpyAsync(block_end, h->blockEnd, nbe * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  h->beCount = nbe;
+  h->beLen = block_len;
+  if (count_blocks) *count_blocks = h->mt.count_blocks(M);
+  return 0;
+}
+
+extern "C" int kg_debug_mt_consume_normals(kg_debug_mt_t h, size_t used, size_t block_len, int use_block_end) {
+  KG_CHECK(h, "kg_debug_mt_consume_normals: null handle");
+  KG_CHECK(!use_block_end || (block_len >= 1 && block_len == h->beLen && used % block_len == 0 && used / block_len <= h->beCount),
+           "kg_debug_mt_consume_normals: `used` is not a block count of the last draw's block_end");
+  KG_HIP(hipSetDevice(h->device));
+  if (h->mt.consume_normals(used, block_len, use_block_end ? h->blockEnd : nullptr, h->stream)) return 1;
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int kg_debug_mt_consume_normals_dev(kg_debug_mt_t h, unsigned long long used_blocks, size_t block_len) {
+  KG_CHECK(h, "kg_debug_mt_consume_normals_dev: null handle");
+  KG_CHECK(block_len >= 1 && block_len == h->beLen && used_blocks <= h->beCount,
+           "kg_debug_mt_consume_normals_dev: more blocks than the last draw's block_end holds");
+  KG_HIP(hipSetDevice(h->device));
+  if (debug_mt_count(h, used_blocks)) return 1;
+  if (h->mt.consume_normals_dev(h->count, block_len, h->blockEnd, h->stream)) return 1;
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int kg_debug_mt_uniforms(kg_debug_mt_t h, size_t M, double *u) {
+  KG_CHECK(h && u, "kg_debug_mt_uniforms: null argument");
+  KG_CHECK(M >= 1 && M <= DEBUG_MT_MAX, "kg_debug_mt_uniforms: 1 <= M <= 2^24");
+  KG_HIP(hipSetDevice(h->device));
+  if (debug_mt_grow(&h->z, &h->zcap, M)) return 1;
+  if (h->mt.uniforms(h->z, M, h->stream)) return 1;
+  KG_HIP(hipMemcpyAsync(u, h->z, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int kg_debug_mt_peek_uniforms(kg_debug_mt_t h, size_t M, double *u) {
+  KG_CHECK(h && u, "kg_debug_mt_peek_uniforms: null argument");
+  KG_CHECK(M >= 1 && M <= DEBUG_MT_MAX, "kg_debug_mt_peek_uniforms: 1 <= M <= 2^24");
+  KG_HIP(hipSetDevice(h->device));
+  if (debug_mt_grow(&h->z, &h->zcap, M)) return 1;
+  if (h->mt.peek_uniforms(h->z, M, h->stream)) return 1;
+  KG_HIP(hipMemcpyAsync(u, h->z, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int kg_debug_mt_consume_words_dev(kg_debug_mt_t h, unsigned long long words) {
+  KG_CHECK(h, "kg_debug_mt_consume_words_dev: null handle");
+  KG_HIP(hipSetDevice(h->device));
+  if (debug_mt_count(h, words)) return 1;
+  if (h->mt.consume_words_dev(h->count, h->stream)) return 1;
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int kg_debug_mt_prefetch(kg_debug_mt_t h, size_t M) {
+  KG_CHECK(h, "kg_debug_mt_prefetch: null handle");
+  KG_CHECK(M >= 1 && M <= DEBUG_MT_MAX, "kg_debug_mt_prefetch: 1 <= M <= 2^24");
+  KG_HIP(hipSetDevice(h->device));
+  return h->mt.prefetch(M, h->stream);
+}
+
+extern "C" int kg_debug_mt_polar_normals_ahead(kg_debug_mt_t h, size_t M, size_t block_len, const double *z,
+                                               size_t z_len, int *launched) {
+  KG_CHECK(h && z && launched, "kg_debug_mt_polar_normals_ahead: null argument");
+  KG_CHECK(M >= 1 && M <= z_len && z_len <= DEBUG_MT_MAX, "kg_debug_mt_polar_normals_ahead: 1 <= M <= z_len <= 2^24");
+  KG_HIP(hipSetDevice(h->device));
+  *launched = 0;
+  if (!h->mt.side_stream()) return 0;  // (polar_normals_ahead launches nothing then)
+  if (debug_mt_grow(&h->z, &h->zcap, z_len)) return 1;
+  KG_HIP(hipMemcpyAsync(h->z, z, z_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  h->beCount = 0;
+  if (h->mt.polar_normals_ahead(h->z, M, block_len, h->stream)) return 1;
+  *launched = 1;
+  return 0;
+}
+
+extern "C" int kg_debug_mt_join(kg_debug_mt_t h, double *z, size_t z_len) {
+  KG_CHECK(h, "kg_debug_mt_join: null handle");
+  KG_CHECK(!z || z_len <= h->zcap, "kg_debug_mt_join: z_len exceeds the handle's buffer");
+  KG_HIP(hipSetDevice(h->device));
+  if (h->mt.join(h->stream)) return 1;
+  if (z) KG_HIP(hipMemcpyAsync(z, h->z, z_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int kg_debug_mt_export_gsl(kg_debug_mt_t h, void *state5000) {
+  KG_CHECK(h && state5000, "kg_debug_mt_export_gsl: null argument");
+  KG_HIP(hipSetDevice(h->device));
+  return h->mt.export_gsl(state5000, h->stream);
+}
+
+extern "C" int kg_debug_mt_state(kg_debug_mt_t h, unsigned long long *out7, unsigned long long *ring_words) {
+  KG_CHECK(h && out7, "kg_debug_mt_state: null argument");
+  KG_HIP(hipSetDevice(h->device));
+  kg::StreamState st;
+  KG_HIP(hipMemcpyAsync(&st, h->mt.state(), sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  KG_HIP(hipStreamSynchronize(h->stream));
+  out7[0] = st.lo, out7[1] = st.pos, out7[2] = st.hi, out7[3] = st.nzero, out7[4] = st.errors;
+  out7[5] = st.last_attempt, out7[6] = st.total_normals;
+  if (ring_words) *ring_words = h->mt.capacity_words();
+  return 0;
+}

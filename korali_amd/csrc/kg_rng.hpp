@@ -111,6 +111,8 @@ class MtStream {
   StreamState *state() { return st_; }
   unsigned long long capacity_words() const { return R_; }
   size_t words_for_normals(size_t M) const;
+  // workgroups of the polar count and scatter passes of an M-normal draw
+  size_t count_blocks(size_t M) const;
 
  private:
   uint32_t *ring_ = nullptr;

@@ -176,6 +176,11 @@ EXPORTED = [
     "kg_debug_cartpole_at",
     "kg_debug_host_tridiag", "kg_debug_host_tridiag_seq", "kg_debug_host_chase",
     "kg_debug_cholesky", "kg_debug_prior_logdens",
+    "kg_debug_mt_open", "kg_debug_mt_close", "kg_debug_mt_import", "kg_debug_mt_count_blocks",
+    "kg_debug_mt_polar_normals", "kg_debug_mt_consume_normals", "kg_debug_mt_consume_normals_dev",
+    "kg_debug_mt_uniforms", "kg_debug_mt_peek_uniforms", "kg_debug_mt_consume_words_dev",
+    "kg_debug_mt_prefetch", "kg_debug_mt_polar_normals_ahead", "kg_debug_mt_join", "kg_debug_mt_export_gsl",
+    "kg_debug_mt_state",
     # VRACER (korali_amd/vracer.py binds their argument types)
     "kg_vracer_create", "kg_vracer_create_discrete", "kg_vracer_destroy", "kg_vracer_hyperparameter_count", "kg_vracer_field_size",
     "kg_vracer_get_field", "kg_vracer_set_field", "kg_vracer_get_scalar", "kg_vracer_set_scalar",
@@ -221,6 +226,21 @@ def lib():
         L.kg_debug_host_chase.argtypes = [sz, vp, vp, C.c_int, sz, vp, vp, vp, sz, vp, vp]
         L.kg_debug_cholesky.argtypes = [C.c_int, sz, vp, vp, vp]
         L.kg_debug_prior_logdens.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, vp, sz, vp, vp]
+        L.kg_debug_mt_open.argtypes = [ip, sz, vp, C.POINTER(vp)]
+        L.kg_debug_mt_close.argtypes = [vp]
+        L.kg_debug_mt_import.argtypes = [vp, vp]
+        L.kg_debug_mt_count_blocks.argtypes = [vp, sz, C.POINTER(sz)]
+        L.kg_debug_mt_polar_normals.argtypes = [vp, sz, sz, sz, sz, vp, sz, vp, C.POINTER(sz)]
+        L.kg_debug_mt_consume_normals.argtypes = [vp, sz, sz, ip]
+        L.kg_debug_mt_consume_normals_dev.argtypes = [vp, C.c_ulonglong, sz]
+        L.kg_debug_mt_uniforms.argtypes = [vp, sz, vp]
+        L.kg_debug_mt_peek_uniforms.argtypes = [vp, sz, vp]
+        L.kg_debug_mt_consume_words_dev.argtypes = [vp, C.c_ulonglong]
+        L.kg_debug_mt_prefetch.argtypes = [vp, sz]
+        L.kg_debug_mt_polar_normals_ahead.argtypes = [vp, sz, sz, vp, sz, C.POINTER(ip)]
+        L.kg_debug_mt_join.argtypes = [vp, vp, sz]
+        L.kg_debug_mt_export_gsl.argtypes = [vp, vp]
+        L.kg_debug_mt_state.argtypes = [vp, vp, C.POINTER(C.c_ulonglong)]
         L.kg_cmaes_generation.argtypes = [vp, sz, ip]
         L.kg_cmaes_field_size.argtypes = [vp, cp, C.POINTER(sz)]
         L.kg_cmaes_get_field.argtypes = [vp, cp, dp, sz]

@@ -1064,6 +1064,107 @@ int kg_nested_synchronize(kg_nested_t h); /* waits and reports device-side error
  * (Nested.cpp.base:584-586).  Host only. */
 int kg_nested_permutation(uint64_t seed, size_t n, size_t *out);
 
+/* ---------------------------------------------------------------- MCMC */
+/* Sampler/MCMC (Metropolis-Hastings with delayed rejection and adaptive
+ * sampling, one chain), MCMC.cpp.base; restated in tests/mcmc_ref.py:
+ *   kg_mcmc_create          MCMC::setInitialConfiguration            MCMC.cpp.base:19-54
+ *   kg_mcmc_run             MCMC::runGeneration :56-101, `count` times in one or a few
+ *                           launches (generateCandidate :170-185, recursiveAlpha :134-168,
+ *                           updateState :187-219, choleskyDecomp :103-132), and the
+ *                           Termination Criteria "Max Samples" (MCMC.config:44-52) and
+ *                           "Max Model Evaluations"
+ *   kg_mcmc_propose         generateCandidate(level)                 :64, :170-185
+ *   kg_mcmc_get_candidate   the sample's "Parameters"                :69
+ *   kg_mcmc_decide          KORALI_GET of logP(x), recursiveAlpha, the accept test :76-90
+ *   kg_mcmc_end_generation  the database push, updateState, _chainLength++ :93-100
+ *   kg_mcmc_database        _sampleDatabase / _sampleEvaluationDatabase
+ * The whole state and both generators live on the device.  exp is the
+ * correctly rounded exp_cr.  recursiveAlpha is a table over the contiguous
+ * sub-paths of (leader, candidate 0, ..., candidate level) instead of a
+ * recursion; a call that returns early on a zero numerator still reports the
+ * denominator the rest of the function would have formed (the reference
+ * leaves it uninitialised and reads it one level later).
+ * Limits: 1 <= N <= 64, 1 <= Rejection Levels <= 8, Max Samples * N <= 2^27. */
+typedef struct kg_mcmc_s *kg_mcmc_t;
+
+enum kg_mcmc_probability {
+  KG_MCMC_HOST = 0,    /* the caller supplies logP(x) (with priors: the log-likelihood) */
+  KG_MCMC_GAUSSIAN = 1 /* -0.5 * sum_d x_d^2, squares as x * x, d ascending */
+};
+/* why kg_mcmc_run returned (bits) */
+enum kg_mcmc_stop {
+  KG_MCMC_MAX_SAMPLES = 1,          /* the database holds max_samples rows */
+  KG_MCMC_MAX_MODEL_EVALUATIONS = 2 /* "Model Evaluation Count" reached the given maximum */
+};
+
+typedef struct {
+  size_t variable_count;           /* N */
+  long long burn_in;               /* "Burn In" */
+  long long leap;                  /* "Leap" */
+  long long rejection_levels;      /* "Rejection Levels" (R) */
+  int use_adaptive_sampling;       /* "Use Adaptive Sampling" */
+  long long non_adaption_period;   /* "Non Adaption Period" */
+  double chain_covariance_scaling; /* "Chain Covariance Scaling" */
+  size_t max_samples;              /* Termination Criteria / "Max Samples": the database's capacity */
+  const double *initial_mean;      /* the variables' "Initial Mean" (N) */
+  const double *initial_sdev;      /* the variables' "Initial Standard Deviation" (N) */
+  int probability_kernel;          /* enum kg_mcmc_probability */
+  /* priors as in kg_tmcmc_cfg; prior_kind NULL: no priors, logP(x) is the kernel's value alone */
+  const double *prior_min;
+  const double *prior_max;
+  const int *prior_kind;
+  uint64_t normal_seed, uniform_seed;
+  size_t window_candidates; /* candidates (N^2 normals and one uniform each) one launch's stream
+                               windows hold (0: default); grown to R if smaller */
+  int device;
+} kg_mcmc_cfg;
+
+int kg_mcmc_create(const kg_mcmc_cfg *cfg, kg_mcmc_t *out);
+int kg_mcmc_destroy(kg_mcmc_t h);
+/* Builtin kernel: up to `count` whole generations first_generation,
+ * first_generation + 1, ... with no host round trip inside a stream window.
+ * Stops before a generation when the database is full and after the one in
+ * which "Model Evaluation Count" reaches max_model_evaluations (0: no limit).
+ * *done (may be NULL) receives the generations completed, *stopped_by (may be
+ * NULL) the enum kg_mcmc_stop bits that hold afterwards. */
+int kg_mcmc_run(kg_mcmc_t h, size_t first_generation, size_t count, size_t max_model_evaluations, size_t *done,
+                int *stopped_by);
+/* The same one level at a time, for probabilities evaluated by the caller:
+ * for level = 0, 1, ... until *accepted or level == R - 1: propose, read the
+ * candidate, decide with its logP(x) (NaN is an error; ignored with a builtin
+ * kernel, may then be passed as 0); then end_generation. */
+int kg_mcmc_propose(kg_mcmc_t h, size_t level);
+int kg_mcmc_get_candidate(kg_mcmc_t h, double *x);
+int kg_mcmc_decide(kg_mcmc_t h, size_t level, double logp, int *accepted);
+int kg_mcmc_end_generation(kg_mcmc_t h, size_t generation);
+/* the database: X (rows x N, may be NULL), logp (rows, may be NULL); *rows
+ * holds the capacity of X / logp in rows on entry and the row count on return */
+int kg_mcmc_database(kg_mcmc_t h, double *X, double *logp, size_t *rows);
+/* named state, keys as in MCMC.config's Internal Settings ("Chain Leader",
+ * "Chain Leader Evaluation", "Chain Candidate", "Chain Candidates
+ * Evaluations", "Cholesky Decomposition Covariance", "Cholesky Decomposition
+ * Chain Covariance", "Chain Mean", "Chain Covariance", "Chain Covariance
+ * Placeholder", "Acceptance Rate", "Acceptance Count", "Proposed Sample
+ * Count", "Chain Length", "Sample Database", "Sample Evaluation Database"),
+ * "Model Evaluation Count" and "Cholesky Failures" (how often the reference
+ * would have warned and kept the old factor); counts travel as doubles.
+ * Setting "Sample Database" sets the row count; "Sample Evaluation Database"
+ * follows with the same rows. */
+int kg_mcmc_field_size(kg_mcmc_t h, const char *name, size_t *n);
+int kg_mcmc_get_field(kg_mcmc_t h, const char *name, double *out, size_t n);
+int kg_mcmc_set_field(kg_mcmc_t h, const char *name, const double *in, size_t n);
+/* 5000-byte GSL states.  which: 0 Normal, 1 Uniform generator. */
+int kg_mcmc_get_rng(kg_mcmc_t h, int which, void *state5000);
+int kg_mcmc_set_rng(kg_mcmc_t h, int which, const void *state5000);
+/* Diagnostics only (any pointer may be NULL): the launches the last
+ * kg_mcmc_run used, how many of them followed an exhausted stream window,
+ * and the window size in candidates. */
+int kg_mcmc_diagnostics(kg_mcmc_t h, size_t *last_windows, size_t *last_relaunches, size_t *window_candidates);
+/* stage timing as kg_cmaes_profile; stages "window", "chain", "consume" */
+int kg_mcmc_profile(kg_mcmc_t h, int enable);
+int kg_mcmc_profile_read(kg_mcmc_t h, const char *stage, double *ms_total, size_t *count);
+int kg_mcmc_synchronize(kg_mcmc_t h); /* waits and reports device-side errors */
+
 /* ------------------------------------------------------- DeepSupervisor
  * Learner/DeepSupervisor on a Supervised Learning problem (feed-forward,
  * float32, one timestep), the whole training step on the device:

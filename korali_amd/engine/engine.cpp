@@ -457,6 +457,9 @@ struct SolverModule {
   virtual std::string type() const = 0;
   // beside each result file, in its directory (VRACER: the training state)
   virtual void saveFiles(const std::string &dir) { (void)dir; }
+  // before runGeneration(g): the first generation >= g after which the engine reads the solver's state (a result
+  // file, console output above Minimal).  A solver that can run generations ahead of the loop stops there.
+  virtual void stateReadAt(size_t gen) { (void)gen; }
   // a Learner evaluates input batches (Experiment::getEvaluation); other solvers do not
   virtual bool evaluate(const std::vector<std::vector<std::vector<float>>> &, std::vector<std::vector<float>> &) {
     return false;
@@ -589,6 +592,7 @@ const KeyList TMCMC_TERMINATION = {"Target Annealing Exponent"};
 const KeyList OPTIMIZATION_KEYS = {"Type", "Num Objectives", "Objective Function", "Constraints",
                                    "Has Discrete Variables", "Objective Kernel"};
 const KeyList BAYESIAN_CUSTOM_KEYS = {"Type", "Likelihood Model", "Likelihood Kernel"};
+const KeyList SAMPLING_KEYS = {"Type", "Probability Function", "Probability Kernel"};
 const KeyList BAYESIAN_REFERENCE_KEYS = {"Type", "Computational Model", "Reference Data", "Likelihood Model"};
 // hierarchical/psi/psi.config, hierarchical/thetaNew/thetaNew.config, hierarchical/theta/theta.config
 const KeyList HIERARCHICAL_PSI_KEYS = {"Type", "Sub Experiments", "Conditional Priors"};
@@ -620,6 +624,7 @@ void rejectUnrecognised(Json &mod, const char *moduleName, std::initializer_list
 
 void rejectProblemUnrecognised(Json &pb, const std::string &pt) {
   if (pt == "optimization") rejectUnrecognised(pb, "Optimization", {OPTIMIZATION_KEYS}, {});
+  else if (pt == "sampling") rejectUnrecognised(pb, "Sampling", {SAMPLING_KEYS}, {});
   else if (pt == "bayesian/custom") rejectUnrecognised(pb, "Custom", {BAYESIAN_CUSTOM_KEYS}, {});
   else if (pt == "bayesian/reference") rejectUnrecognised(pb, "Reference", {BAYESIAN_REFERENCE_KEYS}, {});
   else if (pt == "hierarchical/psi") rejectUnrecognised(pb, "Psi", {HIERARCHICAL_PSI_KEYS}, {});
@@ -2244,6 +2249,338 @@ struct NestedModule : SolverModule {
   }
 
   std::string type() const override { return "Sampler/Nested"; }
+};
+
+// ---------------------------------------------------------------- MCMC
+// MCMC.config
+const KeyList MCMC_KEYS = {
+    // Configuration Settings
+    "Burn In", "Leap", "Rejection Levels", "Use Adaptive Sampling", "Non Adaption Period", "Chain Covariance Scaling",
+    // Internal Settings
+    "Normal Generator", "Uniform Generator", "Cholesky Decomposition Covariance",
+    "Cholesky Decomposition Chain Covariance", "Chain Leader", "Chain Leader Evaluation", "Chain Candidate",
+    "Chain Candidates Evaluations", "Rejection Alphas", "Acceptance Rate", "Acceptance Count", "Proposed Sample Count",
+    "Sample Database", "Sample Evaluation Database", "Chain Mean", "Chain Covariance Placeholder", "Chain Covariance",
+    "Chain Length",
+    // state this build writes: how often the reference would have warned and kept the old factor
+    "Cholesky Failures"};
+const KeyList MCMC_TERMINATION = {"Max Samples"};
+// Variables Configuration of MCMC.config, the variable's own keys and the defaults readVariables writes
+const KeyList MCMC_VARIABLE_KEYS = {"Name", "Initial Mean", "Initial Standard Deviation", "Prior Distribution",
+                                    "Distribution Index", "Lower Bound", "Upper Bound", "Initial Value",
+                                    "Minimum Standard Deviation Update", "Granularity"};
+
+const char *MCMC_SCALARS[] = {"Acceptance Rate", "Chain Leader Evaluation"};
+const char *MCMC_COUNTS[] = {"Acceptance Count", "Proposed Sample Count", "Chain Length", "Model Evaluation Count",
+                             "Cholesky Failures"};
+const char *MCMC_VECTORS[] = {"Chain Leader", "Chain Candidates Evaluations", "Chain Mean",
+                              "Cholesky Decomposition Covariance", "Cholesky Decomposition Chain Covariance",
+                              "Chain Covariance", "Chain Covariance Placeholder"};
+// 'Sample Database' first: it sets the row count 'Sample Evaluation Database' follows
+const char *MCMC_DATABASES[] = {"Sample Database", "Sample Evaluation Database"};
+
+struct McmcModule : SolverModule {
+  kg_mcmc_t h = nullptr;
+  size_t N = 0, burnIn = 0, leap = 1, levels = 1, nonAdaptionPeriod = 0, maxSamples = 5000;
+  bool adaptive = false, sampling = false, bayesian = false, reference = false, builtin = false;
+  double scaling = 1.0, maxGenerations, maxModelEvaluations;
+  size_t fn = 0;  // the Sampling problem's 'Probability Function'
+  LikelihoodSpec lik;
+  PriorSpec ps;
+  // generations kg_mcmc_run has completed ahead of the engine's loop, and the
+  // next generation after which somebody reads the solver's state
+  size_t doneUntil = 0, nextRead = 0;
+  std::vector<std::string> names;
+
+  ~McmcModule() override {
+    if (h) kg_mcmc_destroy(h);
+  }
+
+  McmcModule(Json &js, Seeder &seeds, bool resume, Collective *dist) {
+    Json &sv = js["Solver"];
+    Json &pb = js["Problem"];
+    const std::string pt = canon(str(pb, "Type", ""));
+    if (pt.rfind("hierarchical/", 0) == 0 || (pt != "sampling" && pt != "bayesian/custom" && pt != "bayesian/reference"))
+      fail("The device MCMC path supports problems of type 'Sampling', 'Bayesian/Custom' and 'Bayesian/Reference' "
+           "(is '%s').", pb["Type"].getString().c_str());
+    if (dist)
+      fail("Sampler/MCMC does not shard across ranks: the Distributed conduit is not provided for this solver "
+           "(Sequential or Concurrent).");
+    rejectUnrecognised(sv, "MCMC", {SOLVER_KEYS, MCMC_KEYS}, {SOLVER_TERMINATION, MCMC_TERMINATION});
+    rejectProblemUnrecognised(pb, pt);
+    sampling = pt == "sampling";
+    bayesian = !sampling;
+    reference = pt == "bayesian/reference";
+    if (!js.contains("Variables") || js["Variables"].size() == 0)
+      fail(sampling ? "Sampling Evaluation problems require at least one variable.\n" : "No variables have been defined.");
+    for (size_t i = 0; i < js["Variables"].size(); i++) {
+      Json &v = js["Variables"][i];
+      rejectUnrecognised(v, "MCMC", {MCMC_VARIABLE_KEYS}, {});
+      mandatory(v, "Initial Mean", "MCMC");
+      mandatory(v, "Initial Standard Deviation", "MCMC");
+    }
+    const std::vector<VariableSpec> vars = readVariables(js);
+    N = vars.size();
+    std::vector<double> mean(N), sdev(N);
+    for (size_t d = 0; d < N; d++) {
+      mean[d] = js["Variables"][d]["Initial Mean"].getDouble();
+      names.push_back(vars[d].name);
+      sdev[d] = vars[d].istd;
+    }
+    // MCMC.config Module Defaults
+    const long long burnInS = (long long)num(sv, "Burn In", 0), leapS = (long long)num(sv, "Leap", 1);
+    const long long levelsS = (long long)num(sv, "Rejection Levels", 1);
+    adaptive = flag(sv, "Use Adaptive Sampling", false);
+    const long long napS = (long long)num(sv, "Non Adaption Period", 0);
+    scaling = num(sv, "Chain Covariance Scaling", 1.0);
+    Json &tc = sv["Termination Criteria"];
+    maxGenerations = num(tc, "Max Generations", 1e10);
+    maxModelEvaluations = num(tc, "Max Model Evaluations", 1e9);
+    maxSamples = uint(tc, "Max Samples", 5000);
+    // setInitialConfiguration (MCMC.cpp.base:23-27)
+    if (scaling <= 0.0) fail("Chain Covariance Scaling must be larger 0.0 (is %lf).\n", scaling);
+    if (leapS < 1) fail("Leap must be larger 0 (is %zu).\n", (size_t)leapS);
+    if (burnInS < 0) fail("Burn In must be larger equal 0 (is %zu).\n", (size_t)burnInS);
+    if (levelsS < 1) fail("Rejection Levels must be larger 0 (is %zu).\n", (size_t)levelsS);
+    if (napS < 0) fail("Non Adaption Period must be larger equal 0 (is %zu).\n", (size_t)napS);
+    burnIn = (size_t)burnInS;
+    leap = (size_t)leapS;
+    levels = (size_t)levelsS;
+    nonAdaptionPeriod = (size_t)napS;
+    if (sampling) {
+      // sampling.config: 'Probability Function'; 'Probability Kernel' is this build's device-side model
+      if (pb.contains("Probability Kernel")) {
+        if (canon(pb["Probability Kernel"].getString()) != "gaussian")
+          fail("Unknown 'Probability Kernel' '%s'.", pb["Probability Kernel"].getString().c_str());
+        builtin = true;
+      } else {
+        if (!pb.contains("Probability Function") || !pb["Probability Function"].is_integer())
+          fail("Problem 'Sampling' requires a 'Probability Function' (or the device's 'Probability Kernel').");
+        fn = pb["Probability Function"].getUInt();
+      }
+    } else {
+      ps = readPriors(js, vars, false, "MCMC");
+      lik = readLikelihood(pb, reference);
+      builtin = lik.builtin;
+    }
+    // generators in MCMC.config Internal Settings order: Normal, Uniform
+    Json &gn = sv["Normal Generator"], &gu = sv["Uniform Generator"];
+    gn["Type"] = "Univariate/Normal";
+    gn["Mean"] = 0.0;
+    gn["Standard Deviation"] = 1.0;
+    gu["Type"] = "Univariate/Uniform";
+    gu["Minimum"] = 0.0;
+    gu["Maximum"] = 1.0;
+    kg_mcmc_cfg c{};
+    c.variable_count = N;
+    c.burn_in = burnInS;
+    c.leap = leapS;
+    c.rejection_levels = levelsS;
+    c.use_adaptive_sampling = adaptive ? 1 : 0;
+    c.non_adaption_period = napS;
+    c.chain_covariance_scaling = scaling;
+    c.max_samples = maxSamples;
+    c.initial_mean = mean.data();
+    c.initial_sdev = sdev.data();
+    c.probability_kernel = builtin ? KG_MCMC_GAUSSIAN : KG_MCMC_HOST;
+    if (bayesian) {
+      c.prior_min = ps.pmin.data();
+      c.prior_max = ps.pmax.data();
+      c.prior_kind = ps.pkind.data();
+    }
+    c.normal_seed = seeds.assign(gn);
+    c.uniform_seed = seeds.assign(gu);
+    c.device = solverDevice(js, nullptr);
+    check(kg_mcmc_create(&c, &h));
+    try {  // (the destructor of a partly constructed object does not run)
+      unsigned char st[5000];
+      if (seeds.range(gn, st)) check(kg_mcmc_set_rng(h, 0, st));
+      if (seeds.range(gu, st)) check(kg_mcmc_set_rng(h, 1, st));
+      if (resume) restore(sv);
+    } catch (...) {
+      kg_mcmc_destroy(h);
+      h = nullptr;
+      throw;
+    }
+  }
+
+  void setField(Json &sv, const char *k) {
+    if (!sv.contains(k)) return;
+    std::vector<double> v;
+    if (sv[k].is_array())
+      v = flatten(sv[k]);
+    else if (sv[k].is_number())
+      v.push_back(sv[k].getDouble());
+    else
+      return;
+    size_t n = 0;
+    check(kg_mcmc_field_size(h, k, &n));
+    const std::string key = k;
+    // (generation 0's file holds the reference's empty vectors)
+    if (v.empty() && key != "Sample Database" && key != "Sample Evaluation Database") return;
+    if (kg_mcmc_set_field(h, k, v.data(), v.size()) != 0)
+      fail("Resuming Sampler/MCMC: saved field '%s' has %zu values: %s", k, v.size(), kg_last_error());
+  }
+
+  // MCMC::setConfiguration of a saved state (loadState + resume)
+  void restore(Json &sv) {
+    for (const char *k : MCMC_DATABASES) setField(sv, k);
+    for (const char *k : MCMC_VECTORS) setField(sv, k);
+    setField(sv, "Chain Candidate");
+    for (const char *k : MCMC_SCALARS) setField(sv, k);
+    for (const char *k : MCMC_COUNTS) setField(sv, k);
+  }
+
+  std::vector<double> vector(const char *k) {
+    size_t n = 0;
+    check(kg_mcmc_field_size(h, k, &n));
+    std::vector<double> v(n);
+    check(kg_mcmc_get_field(h, k, v.data(), n));
+    return v;
+  }
+
+  // whether evaluateLogPrior gives -inf at x: outside the support of a prior
+  bool outsidePriors(const std::vector<double> &x) const {
+    for (size_t d = 0; d < N; d++) {
+      const double a = ps.pmin[d], b = ps.pmax[d];
+      switch (ps.pkind[d]) {
+        case KG_PRIOR_UNIFORM:
+          if (!(x[d] >= a && x[d] <= b)) return true;
+          break;
+        case KG_PRIOR_EXPONENTIAL:
+          if (x[d] - a < 0) return true;
+          break;
+        case KG_PRIOR_LOGNORMAL:
+          if (x[d] <= 0) return true;
+          break;
+        default: break;
+      }
+    }
+    return false;
+  }
+
+  // KORALI_START / WAIT / GET of :66-76 through the conduit: Sampling::evaluate
+  // (sampling.cpp.base:11-22) or Bayesian::evaluateLogPosterior's model call
+  double evaluateHost(size_t gen, size_t sampleId, const std::vector<double> &x) {
+    if (bayesian && outsidePriors(x)) return 0.0;  // no model evaluation behind a -inf prior: the device sets -inf
+    double value = 0.0;
+    conduit->evaluateBatch(1, [&](size_t) {
+      Sample s;
+      s["Module"] = "Problem";
+      s["Operation"] = "Evaluate";
+      s["Sample Id"] = (unsigned long long)sampleId;
+      s["Current Generation"] = (unsigned long long)gen;
+      s["Parameters"] = x;
+      if (sampling) {
+        getFunction(fn)(s);
+        if (!s.contains("logP(x)")) fail("The probability function did not assign 'logP(x)' for sample %zu.", sampleId);
+        value = s["logP(x)"].getDouble();
+        if (!std::isfinite(value)) fail("Non finite value of evaluation detected: %f\n", value);
+        s["F(x)"] = value;
+        return;
+      }
+      getFunction(lik.fn)(s);
+      if (reference) s["logLikelihood"] = referenceLoglikelihood(lik.likelihoodModel, lik.referenceData, s);
+      if (!s.contains("logLikelihood"))
+        fail("The likelihood model did not assign 'logLikelihood' for sample %zu.", sampleId);
+      value = s["logLikelihood"].getDouble();
+      if (std::isnan(value)) fail("Sample %zu returned NaN logLikelihood evaluation.\n", sampleId);
+    });
+    return value;
+  }
+
+  void stateReadAt(size_t gen) override { nextRead = gen; }
+
+  void runGeneration(size_t gen) override {
+    if (builtin) {
+      if (gen <= doneUntil) return;  // run ahead in an earlier call
+      // up to the next generation whose state is read; Max Samples and Max
+      // Model Evaluations end the run inside kg_mcmc_run, Max Generations here
+      size_t last = nextRead >= gen ? nextRead : gen;
+      if ((double)last > maxGenerations) last = (size_t)maxGenerations;
+      if (last < gen) last = gen;
+      size_t done = 0;
+      const double limit = std::ceil(std::min(maxModelEvaluations, 9e18));
+      check(kg_mcmc_run(h, gen, last - gen + 1, limit > 0 ? (size_t)limit : 0, &done, nullptr));
+      if (!done) fail("Sampler/MCMC: generation %zu did not run although no termination criterion held.", gen);
+      // (a run that stops short met a criterion: the check before generation gen + done reports it)
+      doneUntil = gen + done - 1;
+      return;
+    }
+    std::vector<double> x(N);
+    const size_t rows = (size_t)vector("Sample Evaluation Database").size();
+    for (size_t level = 0; level < levels; level++) {
+      int accepted = 0;
+      check(kg_mcmc_propose(h, level));
+      check(kg_mcmc_get_candidate(h, x.data()));
+      check(kg_mcmc_decide(h, level, evaluateHost(gen, rows, x), &accepted));
+      if (accepted) break;
+    }
+    check(kg_mcmc_end_generation(h, gen));
+  }
+
+  // criteria evaluated before generation `gen`: _k->_currentGeneration is gen - 1
+  void checkTermination(size_t gen, std::vector<std::string> &met) override {
+    if (gen <= doneUntil) return;  // generation gen already ran: nothing held before it
+    check(kg_mcmc_synchronize(h));
+    if (gen > maxGenerations) met.push_back("Max Generations");
+    if (maxModelEvaluations <= vector("Model Evaluation Count")[0]) met.push_back("Max Model Evaluations");
+    if (vector("Sample Evaluation Database").size() >= maxSamples) met.push_back("Max Samples");  // MCMC.config:44-52
+  }
+
+  void getConfiguration(Json &sv) override {
+    for (const char *k : MCMC_SCALARS) sv[k] = vector(k)[0];
+    for (const char *k : MCMC_COUNTS) sv[k] = (unsigned long long)vector(k)[0];
+    for (const char *k : MCMC_VECTORS) sv[k] = vector(k);
+    sv["Chain Candidate"] = matrixJson(vector("Chain Candidate"), levels, N);
+    const std::vector<double> db = vector("Sample Database");
+    sv["Sample Database"] = matrixJson(db, db.size() / N, N);
+    sv["Sample Evaluation Database"] = vector("Sample Evaluation Database");
+    sv["Rejection Alphas"] = std::vector<double>(levels, 0.0);  // resized, never written (:36)
+    sv["Variable Count"] = (unsigned long long)N;
+    sv["Burn In"] = (unsigned long long)burnIn;
+    sv["Leap"] = (unsigned long long)leap;
+    sv["Rejection Levels"] = (unsigned long long)levels;
+    sv["Use Adaptive Sampling"] = adaptive;
+    sv["Non Adaption Period"] = (unsigned long long)nonAdaptionPeriod;
+    sv["Chain Covariance Scaling"] = scaling;
+    unsigned char st[5000];
+    check(kg_mcmc_get_rng(h, 0, st));
+    sv["Normal Generator"]["Range"] = hexState(st);
+    check(kg_mcmc_get_rng(h, 1, st));
+    sv["Uniform Generator"]["Range"] = hexState(st);
+  }
+
+  // MCMC::finalize (:243-249): the result; its three log lines need a logger, which does not reach finalize
+  void finalize(Json &js) override {
+    const std::vector<double> db = vector("Sample Database");
+    js["Results"]["Sample Database"] = matrixJson(db, db.size() / N, N);
+  }
+
+  // printGenerationAfter (:223-241)
+  void printAfter(const Logger &log) override {
+    log.log(1, "Database Entries %ld\n", (long)vector("Sample Evaluation Database").size());
+    log.log(2, "Accepted Samples: %zu\n", (size_t)vector("Acceptance Count")[0]);
+    log.log(2, "Acceptance Rate Proposals: %.2f%%\n", 100 * vector("Acceptance Rate")[0]);
+    if (log.level < 3) return;
+    const std::vector<double> leader = vector("Chain Leader"), mean = vector("Chain Mean"), cov = vector("Chain Covariance");
+    log.log(3, "Current Sample:\n");
+    for (size_t d = 0; d < N; d++) log.log(3, "         %s = %+6.3e\n", names[d].c_str(), leader[d]);
+    log.log(3, "Current Chain Mean:\n");
+    for (size_t d = 0; d < N; d++) log.log(3, "         %s = %+6.3e\n", names[d].c_str(), mean[d]);
+    log.log(3, "Current Chain Covariance:\n");
+    for (size_t d = 0; d < N; d++) {
+      std::string row;
+      char buf[32];
+      for (size_t e = 0; e <= d; e++) {
+        snprintf(buf, sizeof buf, "         %+6.3e  ", cov[d * N + e]);
+        row += buf;
+      }
+      log.log(3, "%s\n", row.c_str());
+    }
+  }
+
+  std::string type() const override { return "Sampler/MCMC"; }
 };
 
 // --------------------------------------------------------------- TMCMC
@@ -4053,6 +4390,8 @@ void runExperiment(Experiment &e, Conduit &conduit) {
     st.solver.reset(tm);
   } else if (stype == "sampler/nested" || stype == "nested") {
     st.solver.reset(new NestedModule(js, seeds, resume, dist));
+  } else if (stype == "sampler/mcmc" || stype == "mcmc") {
+    st.solver.reset(new McmcModule(js, seeds, resume, dist));
   } else if (stype == "agent/continuous/vracer" || stype == "vracer") {
     // the device rollouts + update of one learner have no exchange step:
     // several GPUs run independent replicas
@@ -4078,7 +4417,7 @@ void runExperiment(Experiment &e, Conduit &conduit) {
     release.keep = true;
   } else {
     fail("Unrecognized solver type '%s' (the device path provides Optimizer/CMAES, Optimizer/MOCMAES, Sampler/TMCMC, "
-         "Sampler/Nested, Agent/Continuous/VRACER, Agent/Discrete/dVRACER and Learner/DeepSupervisor).",
+         "Sampler/Nested, Sampler/MCMC, Agent/Continuous/VRACER, Agent/Discrete/dVRACER and Learner/DeepSupervisor).",
          sv["Type"].getString().c_str());
   }
   clk.mark("setup");
@@ -4111,6 +4450,13 @@ void runExperiment(Experiment &e, Conduit &conduit) {
     if (consoleFreq > 0 && gen % consoleFreq == 0) {
       st.log.log(1, "--------------------------------------------------------------------\n");
       st.log.log(1, "Current Generation: #%zu\n", gen);
+    }
+    {
+      size_t next = (size_t)-1;
+      auto upTo = [&](size_t freq) { next = std::min(next, (gen + freq - 1) / freq * freq); };
+      if (fileOut && fileFreq > 0) upTo(fileFreq);
+      if (consoleFreq > 0 && st.log.level >= 2) upTo((size_t)consoleFreq);
+      solver.stateReadAt(next);
     }
     const auto g0 = std::chrono::steady_clock::now();
     solver.runGeneration(gen);

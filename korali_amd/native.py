@@ -130,6 +130,21 @@ class _NestedCfg(C.Structure):
     ]
 
 
+class _McmcCfg(C.Structure):
+    _fields_ = [
+        ("variable_count", C.c_size_t), ("burn_in", C.c_longlong), ("leap", C.c_longlong),
+        ("rejection_levels", C.c_longlong), ("use_adaptive_sampling", C.c_int),
+        ("non_adaption_period", C.c_longlong), ("chain_covariance_scaling", C.c_double),
+        ("max_samples", C.c_size_t), ("initial_mean", C.POINTER(C.c_double)), ("initial_sdev", C.POINTER(C.c_double)),
+        ("probability_kernel", C.c_int), ("prior_min", C.POINTER(C.c_double)), ("prior_max", C.POINTER(C.c_double)),
+        ("prior_kind", C.POINTER(C.c_int)), ("normal_seed", C.c_uint64), ("uniform_seed", C.c_uint64),
+        ("window_candidates", C.c_size_t), ("device", C.c_int),
+    ]
+
+
+MCMC_KERNELS = {"gaussian": 1}
+MCMC_STOP = {1: "Max Samples", 2: "Max Model Evaluations"}
+
 NESTED_METHODS = {"box": 0, "ellipse": 1, "multi ellipse": 2}
 NESTED_TERMINATION = {1: "Min Log Evidence Delta", 2: "Max Effective Sample Size", 4: "Max Log Likelihood"}
 
@@ -161,6 +176,10 @@ EXPORTED = [
     "kg_nested_process", "kg_nested_finalize", "kg_nested_field_size", "kg_nested_get_field", "kg_nested_set_field",
     "kg_nested_get_rng", "kg_nested_set_rng", "kg_nested_diagnostics", "kg_nested_profile",
     "kg_nested_profile_read", "kg_nested_synchronize", "kg_nested_permutation",
+    "kg_mcmc_create", "kg_mcmc_destroy", "kg_mcmc_run", "kg_mcmc_propose", "kg_mcmc_get_candidate", "kg_mcmc_decide",
+    "kg_mcmc_end_generation", "kg_mcmc_database", "kg_mcmc_field_size", "kg_mcmc_get_field", "kg_mcmc_set_field",
+    "kg_mcmc_get_rng", "kg_mcmc_set_rng", "kg_mcmc_diagnostics", "kg_mcmc_profile", "kg_mcmc_profile_read",
+    "kg_mcmc_synchronize",
     "kg_supervisor_create", "kg_supervisor_destroy", "kg_supervisor_hyperparameter_count",
     "kg_supervisor_set_training_data", "kg_supervisor_train", "kg_supervisor_forward",
     "kg_supervisor_backward_direct", "kg_supervisor_field_size", "kg_supervisor_get_field",
@@ -310,6 +329,23 @@ def lib():
         L.kg_nested_profile.argtypes = [vp, ip]
         L.kg_nested_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_nested_permutation.argtypes = [C.c_uint64, sz, C.POINTER(sz)]
+        L.kg_mcmc_create.argtypes = [C.POINTER(_McmcCfg), C.POINTER(vp)]
+        for f in ("kg_mcmc_destroy", "kg_mcmc_synchronize"):
+            getattr(L, f).argtypes = [vp]
+        L.kg_mcmc_run.argtypes = [vp, sz, sz, sz, C.POINTER(sz), C.POINTER(ip)]
+        L.kg_mcmc_propose.argtypes = [vp, sz]
+        L.kg_mcmc_get_candidate.argtypes = [vp, dp]
+        L.kg_mcmc_decide.argtypes = [vp, sz, C.c_double, C.POINTER(ip)]
+        L.kg_mcmc_end_generation.argtypes = [vp, sz]
+        L.kg_mcmc_database.argtypes = [vp, dp, dp, C.POINTER(sz)]
+        L.kg_mcmc_field_size.argtypes = [vp, cp, C.POINTER(sz)]
+        L.kg_mcmc_get_field.argtypes = [vp, cp, dp, sz]
+        L.kg_mcmc_set_field.argtypes = [vp, cp, dp, sz]
+        L.kg_mcmc_get_rng.argtypes = [vp, ip, vp]
+        L.kg_mcmc_set_rng.argtypes = [vp, ip, vp]
+        L.kg_mcmc_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 3
+        L.kg_mcmc_profile.argtypes = [vp, ip]
+        L.kg_mcmc_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_tmcmc_create.argtypes = [C.POINTER(_TmcmcCfg), C.POINTER(vp)]
         for f in ("kg_tmcmc_destroy", "kg_tmcmc_synchronize", "kg_tmcmc_evaluate", "kg_tmcmc_evaluate_prior"):
             getattr(L, f).argtypes = [vp]
@@ -964,6 +1000,143 @@ class NestedDevice:
     def profile_read(self, stage):
         ms, n = C.c_double(), C.c_size_t()
         check(self._L.kg_nested_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
+class McmcDevice:
+    """One Sampler/MCMC chain (Metropolis-Hastings with delayed rejection and
+    adaptive sampling) on one MI355X (kg_mcmc_t).  probability: "gaussian", or
+    None when the caller evaluates logP(x) (the stepping methods).  With
+    prior_kinds (PRIOR_KINDS names or numbers; prior_min / prior_max their two
+    parameters) logP = logPrior + the kernel's or the caller's value.
+    Generator indices for rng_state / set_rng_state: 0 Normal, 1 Uniform."""
+
+    def __init__(self, N, initial_mean, initial_sdev, burn_in=0, leap=1, rejection_levels=1,
+                 use_adaptive_sampling=False, non_adaption_period=0, chain_covariance_scaling=1.0, max_samples=5000,
+                 probability="gaussian", prior_kinds=None, prior_min=None, prior_max=None, normal_seed=0,
+                 uniform_seed=0, window_candidates=0, device=0):
+        lb = lib()
+        self.N, self.R = int(N), int(rejection_levels)
+        self._arrays = [_vec(initial_mean, self.N, np.nan), _vec(initial_sdev, self.N, np.nan)]
+        cfg = _McmcCfg()
+        cfg.variable_count, cfg.burn_in, cfg.leap, cfg.rejection_levels = self.N, int(burn_in), int(leap), self.R
+        cfg.use_adaptive_sampling = int(bool(use_adaptive_sampling))
+        cfg.non_adaption_period = int(non_adaption_period)
+        cfg.chain_covariance_scaling = float(chain_covariance_scaling)
+        cfg.max_samples = int(max_samples)
+        cfg.initial_mean, cfg.initial_sdev = [_dptr(a) for a in self._arrays]
+        cfg.probability_kernel = 0 if probability is None else (
+            MCMC_KERNELS[probability.lower()] if isinstance(probability, str) else int(probability))
+        if prior_kinds is not None:
+            kinds = [PRIOR_KINDS[k.lower()] if isinstance(k, str) else int(k) for k in prior_kinds]
+            self._kinds = (C.c_int * max(self.N, 1))(*kinds)
+            self._arrays += [_vec(prior_min, self.N, np.nan), _vec(prior_max, self.N, np.nan)]
+            cfg.prior_kind = self._kinds
+            cfg.prior_min, cfg.prior_max = [_dptr(a) for a in self._arrays[2:]]
+        cfg.normal_seed = int(normal_seed) & (2**64 - 1)
+        cfg.uniform_seed = int(uniform_seed) & (2**64 - 1)
+        cfg.window_candidates, cfg.device = int(window_candidates), int(device)
+        h = C.c_void_p()
+        check(lb.kg_mcmc_create(C.byref(cfg), C.byref(h)))
+        self.h = h
+        self._L = lb
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.kg_mcmc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # whole generations, builtin kernel
+    def run(self, first_generation, count, max_model_evaluations=0):
+        """-> (generations completed, names of the stopping criteria that hold)"""
+        done, t = C.c_size_t(0), C.c_int(0)
+        check(self._L.kg_mcmc_run(self.h, int(first_generation), int(count), int(max_model_evaluations),
+                                  C.byref(done), C.byref(t)))
+        return done.value, [n for b, n in MCMC_STOP.items() if t.value & b]
+
+    # one level at a time, for probabilities evaluated by the caller
+    def propose(self, level):
+        check(self._L.kg_mcmc_propose(self.h, int(level)))
+
+    def candidate(self):
+        x = np.empty(self.N)
+        check(self._L.kg_mcmc_get_candidate(self.h, _dptr(x)))
+        return x
+
+    def decide(self, level, logp=0.0):
+        a = C.c_int(0)
+        check(self._L.kg_mcmc_decide(self.h, int(level), float(logp), C.byref(a)))
+        return bool(a.value)
+
+    def end_generation(self, generation):
+        check(self._L.kg_mcmc_end_generation(self.h, int(generation)))
+
+    def generation(self, generation, logp):
+        """one generation with logp(x) evaluated by the caller; -> accepted"""
+        accepted = False
+        for level in range(self.R):
+            self.propose(level)
+            accepted = self.decide(level, logp(self.candidate()))
+            if accepted:
+                break
+        self.end_generation(generation)
+        return accepted
+
+    def database(self):
+        """-> (Sample Database rows x N, Sample Evaluation Database)"""
+        rows = C.c_size_t(0)
+        check(self._L.kg_mcmc_database(self.h, None, None, C.byref(rows)))
+        X, lp = np.empty((rows.value, self.N)), np.empty(rows.value)
+        check(self._L.kg_mcmc_database(self.h, _dptr(X), _dptr(lp), C.byref(rows)))
+        return X, lp
+
+    def synchronize(self):
+        check(self._L.kg_mcmc_synchronize(self.h))
+
+    # state
+    def field_size(self, name):
+        n = C.c_size_t()
+        check(self._L.kg_mcmc_field_size(self.h, name.encode(), C.byref(n)))
+        return n.value
+
+    def __getitem__(self, name):
+        n = self.field_size(name)
+        out = np.empty(n)
+        check(self._L.kg_mcmc_get_field(self.h, name.encode(), _dptr(out), n))
+        return out
+
+    def __setitem__(self, name, value):
+        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
+        check(self._L.kg_mcmc_set_field(self.h, name.encode(), _dptr(a), a.size))
+
+    def rng_state(self, which=0):
+        buf = C.create_string_buffer(5000)
+        check(self._L.kg_mcmc_get_rng(self.h, int(which), buf))
+        return buf.raw
+
+    def set_rng_state(self, state, which=0):
+        assert len(state) == 5000
+        buf = C.create_string_buffer(bytes(state), 5000)
+        check(self._L.kg_mcmc_set_rng(self.h, int(which), buf))
+
+    def diagnostics(self):
+        """(launches the last run used, relaunches after an exhausted window, window size in candidates)"""
+        v = [C.c_size_t() for _ in range(3)]
+        check(self._L.kg_mcmc_diagnostics(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def profile(self, enable=True):
+        check(self._L.kg_mcmc_profile(self.h, int(enable)))
+
+    def profile_read(self, stage):
+        ms, n = C.c_double(), C.c_size_t()
+        check(self._L.kg_mcmc_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
 

@@ -21,6 +21,7 @@
 #include "kg_common.hpp"
 #include "kg_chains.hpp"
 #include "kg_eigen.hpp"
+#include "kg_profile.hpp"
 #include "kg_rng.hpp"
 #include <chrono>
 
@@ -2801,34 +2802,10 @@ struct kg_cmaes_s {
   unsigned *meanArrived = nullptr;  // k_mean3<true>'s arrival counter (zero from create's fill, then monotonic)
   unsigned meanTarget = 0;          // its value once the launch enqueued last has arrived
   MtStream normal, uniform;
-  // profiling
-  bool profile = false;
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, hipEvent_t> openMarks;  // kg_cmaes_profile_mark begun, not ended
-  std::map<std::string, std::pair<double, size_t>> prof;
+  StageTimes times;  // profiling
 };
 
 namespace {
-
-struct Stage {
-  kg_cmaes_s *h;
-  std::string name;
-  hipEvent_t a = nullptr, b = nullptr;
-  hipStream_t s;
-  Stage(kg_cmaes_s *h_, const char *n, hipStream_t on = nullptr) : h(h_), name(n), s(on ? on : h_->stream) {
-    if (h->profile) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, s);
-    }
-  }
-  ~Stage() {
-    if (h->profile) {
-      (void)hipEventRecord(b, s);
-      h->pending.emplace_back(name, a, b);
-    }
-  }
-};
 
 // The plain draw's consume (one thread advancing the Normal stream's state)
 // is deferred by kg_cmaes_sample: nothing between the draw and C's hand-off
@@ -2839,32 +2816,22 @@ struct Stage {
 int flush_consume(kg_cmaes_s *h) {
   if (!h->consumePending) return 0;
   h->consumePending = false;
-  Stage st(h, "rng_consume");
+  Stage st(h->times, h->stream, "rng_consume");
   return h->normal.consume_normals_dev(h->usedBlocks, h->N, h->blockEnd, h->stream);
 }
 
-// eigensolver stage profiling: device stages by events, host stages by clock
+// eigensolver stage profiling (the eigensolver's C callback): device stages
+// by events (phase 0 begins, 1 ends), host stages by clock (2 begins, 3 ends)
 void eig_prof(void *ctx, const char *stage, int phase) {
   auto *h = (kg_cmaes_s *)ctx;
-  if (!h->profile) return;
-  static thread_local hipEvent_t a;
+  if (!h->times.on) return;
   static thread_local std::chrono::steady_clock::time_point t0;
-  if (phase == 0) {
-    (void)hipEventCreate(&a);
-    (void)hipEventRecord(a, h->stream);
-  } else if (phase == 1) {
-    hipEvent_t b;
-    (void)hipEventCreate(&b);
-    (void)hipEventRecord(b, h->stream);
-    h->pending.emplace_back(stage, a, b);
-  } else if (phase == 2) {
+  if (phase < 2)  // (status dropped: an end whose begin fell before profiling was switched on records nothing)
+    (void)h->times.mark(h->stream, stage, phase);
+  else if (phase == 2)
     t0 = std::chrono::steady_clock::now();
-  } else {
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    auto &p = h->prof[stage];
-    p.first += ms;
-    p.second += 1;
-  }
+  else
+    h->times.add(stage, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 // KORALI_AMD_RUN_PHASES=1: kg_cmaes_create's phases on stderr
@@ -2884,32 +2851,6 @@ struct CreateClock {
     if (on) fprintf(stderr, "[korali_amd cmaes create]%s\n", text.c_str());
   }
 };
-
-template <typename T>
-int dalloc(T **p, size_t n, bool wait = true) {
-  if (n == 0) n = 1;
-  KG_HIP(dev_alloc(p, n * sizeof(T)));
-  if (wait ? zero_fill(*p, n * sizeof(T)) : zero_fill_async(*p, n * sizeof(T))) return 1;
-  return 0;
-}
-// kg_cmaes_create's buffers: zero fills queued on the null stream, waited for
-// once after the last one
-template <typename T>
-int dalloc_q(T **p, size_t n) {
-  return dalloc(p, n, false);
-}
-
-void gsl_seed_state(uint64_t seed, unsigned char *out5000) {
-  uint64_t mt[624];
-  uint64_t s = seed & 0xffffffffULL;
-  if (s == 0) s = 4357;
-  mt[0] = s;
-  for (int i = 1; i < 624; i++) mt[i] = (1812433253ULL * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint64_t)i) & 0xffffffffULL;
-  memset(out5000, 0, 5000);
-  memcpy(out5000, mt, sizeof(mt));
-  int32_t mti = 624;
-  memcpy(out5000 + 624 * 8, &mti, 4);
-}
 
 __global__ void k_collect_errors(CmaesScalars *sc, const StreamState *a, const StreamState *b) {
   sc->errors |= a->errors | b->errors;
@@ -3298,11 +3239,7 @@ int kg_cmaes_destroy(kg_cmaes_t h) {
                   (void *)h->pairC, (void *)h->pairCnt, (void *)h->listDev, (void *)h->dzT, (void *)h->shardPos,
                   (void *)h->shardCounts, (void *)h->rows, (void *)h->covPack, (void *)h->meanArrived})
     if (p) dev_release(p);
-  for (auto &t : h->pending) {
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  for (auto &m : h->openMarks) (void)hipEventDestroy(m.second);
+  h->times.release();
   if (h->stream2) {
     (void)hipStreamSynchronize(h->stream2);
     stream_release(h->stream2);
@@ -3315,7 +3252,7 @@ int kg_cmaes_destroy(kg_cmaes_t h) {
 }
 
 int kg_cmaes_initialize(kg_cmaes_t h) {
-  Stage st(h, "init");
+  Stage st(h->times, h->stream, "init");
   h->stateDirty = true;
   // setInitialConfiguration (:54-66, :132-170): CCMA-ES starts in the viability regime
   h->viability = h->nc > 0;
@@ -3342,7 +3279,7 @@ int kg_cmaes_initialize(kg_cmaes_t h) {
 }
 
 static int cmaes_eigen(kg_cmaes_t h) {
-  Stage st(h, "eigen");
+  Stage st(h->times, h->stream, "eigen");
   h->eig.trace = h->eigTrace;
   return h->eig.run(h->C, h->cfg.diagonal_covariance, h->B, h->D, &h->sc->minEig, &h->sc->maxEig,
                     &h->sc->eigenFailures, &h->sc->errors, h->stream, eig_prof, h);
@@ -3476,11 +3413,11 @@ static int cmaes_resample(kg_cmaes_t h) {
   for (int round = 0;; round++) {
     if (round > 0) {
       h->resamplingRounds++;
-      Stage st(h, "rng_polar");
+      Stage st(h->times, h->stream, "rng_polar");
       if (h->normal.polar_normals(h->Z, nb * N, N, h->blockEnd, h->stream)) return 1;
     }
     {
-      Stage st(h, "transform");
+      Stage st(h->times, h->stream, "transform");
       KG_HIP(hipMemsetAsync(h->infeas, 0, xr * sizeof(int), h->stream));
       if (cmaes_transform(h, xr, h->Xall, h->BDZall, 0, h->mirrored ? 1 : 0)) return 1;
       if (h->hasDiscrete) {
@@ -3506,7 +3443,7 @@ static int cmaes_resample(kg_cmaes_t h) {
       }
     }
     {
-      Stage st(h, "rng_consume");
+      Stage st(h->times, h->stream, "rng_consume");
       if (h->normal.consume_normals_dev(h->usedBlocks, N, h->blockEnd, h->stream)) return 1;
     }
     int se[2] = {0, 0};
@@ -3554,7 +3491,7 @@ static bool fused_draw(kg_cmaes_t h, int objective) {
          h->shards == 1 && h->R == 0 && !h->finiteBounds && !h->hasDiscrete && h->nc == 0 && h->trW == 0;
 }
 static int cmaes_transform_obj(kg_cmaes_t h, int objective) {
-  Stage st(h, "transform");
+  Stage st(h->times, h->stream, "transform");
   hipLaunchKernelGGL(k_transform_obj, dim3(tr_grid<TO_BM, TO_BN>(h->lam, h->N)), dim3(256), 0, h->stream, h->N, h->lam,
                      h->Z, h->B, h->D, h->mean, h->sc, h->lb, h->ub, h->X, h->BDZ, h->infeas, h->mirrored ? 1 : 0,
                      objective, h->F, (double)h->lam);
@@ -3573,7 +3510,7 @@ static int cmaes_sample(kg_cmaes_t h, int objective, bool *evaluated) {
   const bool fused = fused_draw(h, objective);
   if (cmaes_eigen(h)) return 1;
   {
-    Stage st(h, "rng_polar");  // what of the producer + polar pass the eigensolver did not hide
+    Stage st(h->times, h->stream, "rng_polar");  // what of the producer + polar pass the eigensolver did not hide
     if (h->normal.join(h->stream)) return 1;
   }
   bool redraw = h->R > 0;
@@ -3592,7 +3529,7 @@ static int cmaes_sample(kg_cmaes_t h, int objective, bool *evaluated) {
     if (cmaes_transform_obj(h, objective)) return 1;
     *evaluated = true;
   } else {
-    Stage st(h, "transform");
+    Stage st(h->times, h->stream, "transform");
     // no redraw possible: the population is the first lambda blocks; a shard
     // transforms its own rows only
     const int t0 = h->replSample ? 0 : h->r0, t1 = h->replSample ? h->lam : h->r1;
@@ -3626,7 +3563,7 @@ int kg_cmaes_sample_eval(kg_cmaes_t h, int objective) {
 
 int kg_cmaes_eval_builtin(kg_cmaes_t h, int objective) {
   KG_CHECK(objective >= 0 && objective <= 2, "unknown builtin objective");
-  Stage st(h, "objective");
+  Stage st(h->times, h->stream, "objective");
   const int rows = h->r1 - h->r0;
   if (h->N <= 128)
     hipLaunchKernelGGL(k_objective2, dim3((rows + OB2_R - 1) / OB2_R), dim3(256), ob2_lds_bytes(h->N), h->stream,
@@ -3672,7 +3609,7 @@ int kg_cmaes_set_gradients(kg_cmaes_t h, const double *G) {
 static int cmaes_sort(kg_cmaes_t h) {
   const int L = h->lam;
   {
-    Stage st(h, "sort");
+    Stage st(h->times, h->stream, "sort");
     int P2 = 1;
     while (P2 < L) P2 <<= 1;
     if (L <= RANK_MAX && L > 256) {
@@ -3702,7 +3639,7 @@ static int cmaes_sort(kg_cmaes_t h) {
 static int cmaes_sigma(kg_cmaes_t h, size_t gen) {
   const int N = h->N, mu = h->mu;
   {
-    Stage st(h, "sigma");
+    Stage st(h->times, h->stream, "sigma");
     if (h->hasDiscrete)
       hipLaunchKernelGGL(k_discrete_masks, dim3(1), dim3(64), 0, h->stream, N, h->lam, h->gran, h->C, h->mask,
                          h->maskSigma, h->sc);
@@ -3724,8 +3661,8 @@ static int cmaes_sigma(kg_cmaes_t h, size_t gen) {
 // up: measured round 5, C4 (N = 512) 3.75 -> 2.14 ms per generation on lane
 // chains, C2 (N = 128: 36 tiles, a third of the chip) 0.036 -> 0.060 ms.
 // Either kernel picks Markstein quotients or true division per launch from
-// k_rankmu_prep's range flag.  While profiling, prof["adaptC_row" /
-// "adaptC_lane"] counts the launches (a host count, no events).
+// k_rankmu_prep's range flag.  While profiling, stage "adaptC_row" /
+// "adaptC_lane" counts the launches (a host count, no events).
 static void cmaes_adaptC_exact(kg_cmaes_t h, int rank, int ranks, double *pack) {
   const int N = h->N;
   const bool lane = N >= h->laneMin;
@@ -3738,7 +3675,7 @@ static void cmaes_adaptC_exact(kg_cmaes_t h, int rank, int ranks, double *pack) 
   else
     hipLaunchKernelGGL(k_adaptC_row, dim3(t1 - t0), dim3(AR_NT), 0, h->stream, N, h->mu, h->cfg.diagonal_covariance,
                        h->Yc, h->Tt, h->pc, h->C, h->sc, t0, pack);
-  if (h->profile) h->prof[lane ? "adaptC_lane" : "adaptC_row"].second += 1;
+  if (h->times.on) h->times.count(lane ? "adaptC_lane" : "adaptC_row");
 }
 
 // the exact factors Yc / T of the selected rows in Y (k_rankmu_prep)
@@ -4030,7 +3967,7 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
   // the separate kernels.
   const bool plain = plain_update(h);
   if (plain) {
-    Stage st(h, "sort");  // the ranking with the selection's scatter (k_rank_select)
+    Stage st(h->times, h->stream, "sort");  // the ranking with the selection's scatter (k_rank_select)
     hipLaunchKernelGGL(k_rank_select, dim3((h->lam + 15) / 16), dim3(256), (size_t)h->lam * sizeof(double), h->stream,
                        h->lam, N, mu, (unsigned long long)generation, h->F, h->idx, h->X, h->w, h->mean, h->prevMean,
                        h->Y, h->currBestVars, h->bestEverVars, h->sc, h->Yc, h->Tt);
@@ -4039,7 +3976,7 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
     return 1;
   }
   {
-    Stage st(h, "mean_paths");
+    Stage st(h->times, h->stream, "mean_paths");
     if (ccm) {
       std::vector<int> viol(h->lam);
       for (int i = 0; i < h->lam; i++) viol[i] = h->cCnt[i] > 0 ? 1 : 0;
@@ -4067,7 +4004,7 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
     if (h->cfg.cov_mode == KG_COV_MFMA) {
       KG_HIP(hipEventRecord(h->evY, h->stream));
       KG_HIP(hipStreamWaitEvent(h->stream2, h->evY, 0));
-      Stage st(h, "rankmu_mfma", h->stream2);
+      Stage st(h->times, h->stream2, "rankmu_mfma");
       hipLaunchKernelGGL(k_rankmu_tile<false>, dim3(rankmu_grid(N, h->kslices)), dim3(256), 0, h->stream2, N, mu,
                          (const int *)nullptr, h->kslices, h->Y, (const int *)nullptr, h->w, h->prevMean, h->sc,
                          h->covPart);
@@ -4092,7 +4029,7 @@ int kg_cmaes_update(kg_cmaes_t h, size_t generation) {
     }
   }
   {
-    Stage st(h, "covariance");
+    Stage st(h->times, h->stream, "covariance");
     if (h->cfg.cov_mode == KG_COV_MFMA) {
       KG_HIP(hipStreamWaitEvent(h->stream, h->evC, 0));
       cmaes_adaptC_combine(h, h->kslices, h->covPart, 0);
@@ -4111,7 +4048,7 @@ int kg_cmaes_update_partial(kg_cmaes_t h, size_t generation) {
   const int N = h->N, mu = h->mu;
   if (cmaes_sort(h)) return 1;
   {
-    Stage st(h, "mean_paths");
+    Stage st(h->times, h->stream, "mean_paths");
     hipLaunchKernelGGL(k_update_best, dim3(1), dim3(256), 0, h->stream, N, mu, h->cfg.mu_type,
                        (unsigned long long)generation, (const double *)nullptr, h->F, h->idx, h->w, h->currBestVars,
                        h->bestEverVars, h->sc, (const int *)nullptr, h->lam);
@@ -4136,7 +4073,7 @@ int kg_cmaes_update_partial(kg_cmaes_t h, size_t generation) {
     KG_HIP(hipGetLastError());
   }
   {
-    Stage st(h, "covariance");
+    Stage st(h->times, h->stream, "covariance");
     const int ntiles = cov_tiles(N);
     hipLaunchKernelGGL(k_rankmu_tile<true>, dim3(rankmu_grid(N, h->kslices)), dim3(256), 0, h->stream, N, 0,
                        h->shardCnt, h->kslices, h->Y, h->kidx, h->w, h->mean, h->sc, h->covPart);  // mean not yet advanced
@@ -4169,7 +4106,7 @@ int kg_cmaes_update_rows(kg_cmaes_t h, size_t generation) {
   const int N = h->N, mu = h->mu;
   const int per = h->lam / h->shards;
   {
-    Stage st(h, "mean_paths");
+    Stage st(h->times, h->stream, "mean_paths");
     hipLaunchKernelGGL(k_shard_unpack, dim3(mu), dim3(128), 0, h->stream, N, per, h->shards, h->idx, h->shardPos,
                        h->shardCounts, (const double *)h->rows, h->X, h->Y, h->mean, h->prevMean, h->currBestVars,
                        h->bestEverVars, h->sc);
@@ -4180,7 +4117,7 @@ int kg_cmaes_update_rows(kg_cmaes_t h, size_t generation) {
   {
     // this rank's contiguous share of the covariance tiles, each element's
     // chain in the reference's order
-    Stage st(h, "covariance");
+    Stage st(h->times, h->stream, "covariance");
     const size_t npk = (size_t)N * (N + 1) / 2;
     hipLaunchKernelGGL(k_fill_min_i64, dim3((unsigned)std::min<size_t>((npk + 255) / 256, 1024)), dim3(256), 0,
                        h->stream, npk, (long long *)h->covPack);
@@ -4194,7 +4131,7 @@ int kg_cmaes_update_rows(kg_cmaes_t h, size_t generation) {
 int kg_cmaes_update_finalize(kg_cmaes_t h, size_t generation) {
   const int N = h->N;
   if (h->covPack) {
-    Stage st(h, "covariance");
+    Stage st(h->times, h->stream, "covariance");
     hipLaunchKernelGGL(k_shard_cov_unpack, dim3(N), dim3(256), 0, h->stream, N, (const double *)h->covPack, h->C);
     KG_HIP(hipGetLastError());
     if (early_publish(h)) return 1;
@@ -4202,14 +4139,14 @@ int kg_cmaes_update_finalize(kg_cmaes_t h, size_t generation) {
     return cmaes_sigma(h, generation);
   }
   {
-    Stage st(h, "mean_paths");
+    Stage st(h->times, h->stream, "mean_paths");
     hipLaunchKernelGGL(k_shard_finalize, dim3((N + 255) / 256), dim3(256), 0, h->stream, N, h->part, h->mean,
                        h->prevMean, h->meanUpdate, h->currBestVars, h->bestEverVars, h->sc);
     KG_HIP(hipGetLastError());
     if (cmaes_mean_paths(h, generation, false)) return 1;  // (k_shard_finalize formed the mean)
   }
   {
-    Stage st(h, "covariance");
+    Stage st(h->times, h->stream, "covariance");
     cmaes_adaptC_combine(h, 1, h->part + 2 * (size_t)N, 1);
     KG_HIP(hipGetLastError());
   }
@@ -4474,53 +4411,21 @@ int kg_cmaes_population_size(kg_cmaes_t h, size_t *lambda, size_t *mu) {
 }
 
 int kg_cmaes_profile(kg_cmaes_t h, int enable) {
-  h->profile = enable != 0;
+  KG_CHECK(h, "kg_cmaes_profile: null handle");
+  h->times.on = enable != 0;
   return 0;
 }
 
 int kg_cmaes_profile_mark(kg_cmaes_t h, const char *stage, int phase) {
-  if (!h || !stage || (phase != 0 && phase != 1)) return 1;
-  hipEvent_t e;
-  KG_HIP(hipEventCreate(&e));
-  KG_HIP(hipEventRecord(e, h->stream));
-  if (phase == 0) {
-    auto it = h->openMarks.find(stage);
-    if (it != h->openMarks.end()) (void)hipEventDestroy(it->second);
-    h->openMarks[stage] = e;
-    return 0;
-  }
-  auto it = h->openMarks.find(stage);
-  if (it == h->openMarks.end()) {
-    (void)hipEventDestroy(e);
-    return 1;
-  }
-  h->pending.emplace_back(stage, it->second, e);
-  h->openMarks.erase(it);
-  return 0;
+  KG_CHECK(h, "kg_cmaes_profile_mark: null handle");
+  KG_CHECK(stage && (phase == 0 || phase == 1), "kg_cmaes_profile_mark: null stage, or a phase other than 0 and 1");
+  return h->times.mark(h->stream, stage, phase);
 }
 
 int kg_cmaes_profile_read(kg_cmaes_t h, const char *stage, double *ms_total, size_t *count) {
-  KG_HIP(hipStreamSynchronize(h->stream));
-  for (auto &t : h->pending) {
-    float ms = 0.f;
-    KG_HIP(hipEventElapsedTime(&ms, std::get<1>(t), std::get<2>(t)));
-    auto &p = h->prof[std::get<0>(t)];
-    p.first += ms;
-    p.second += 1;
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  h->pending.clear();
-  auto it = h->prof.find(stage);
-  if (it == h->prof.end()) {
-    *ms_total = 0;
-    *count = 0;
-  } else {
-    *ms_total = it->second.first;
-    *count = it->second.second;
-    h->prof.erase(it);
-  }
-  return 0;
+  KG_CHECK(h, "kg_cmaes_profile_read: null handle");
+  KG_CHECK(ms_total && count, "kg_cmaes_profile_read: null output");
+  return h->times.read(h->stream, stage, ms_total, count);
 }
 
 }  // extern "C"

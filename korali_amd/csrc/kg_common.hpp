@@ -96,6 +96,20 @@ inline int zero_fill_async(void *p, size_t bytes) {
   KG_HIP(hipMemsetAsync(p, 0, bytes, nullptr));
   return 0;
 }
+// a zeroed device array of n elements (one when n is 0) for a handle
+template <typename T>
+inline int dalloc(T **p, size_t n, bool wait = true) {
+  if (n == 0) n = 1;
+  KG_HIP(dev_alloc(p, n * sizeof(T)));
+  if (wait ? zero_fill(*p, n * sizeof(T)) : zero_fill_async(*p, n * sizeof(T))) return 1;
+  return 0;
+}
+// kg_cmaes_create's buffers: zero fills queued on the null stream, waited for
+// once after the last one
+template <typename T>
+inline int dalloc_q(T **p, size_t n) {
+  return dalloc(p, n, false);
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is per kernel and process-wide,
 // while handles of different sizes need different amounts: the attribute only

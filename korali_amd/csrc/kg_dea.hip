@@ -41,6 +41,7 @@
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
 #include "kg_gsl.hpp"
+#include "kg_profile.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -368,31 +369,10 @@ struct kg_dea_s {
   bool initialized = false;
   MtStream uniform;
   unsigned char normalState[5000];  // the Normal Generator: seeded, saved, never drawn from
-  bool profile = false;
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, std::pair<double, size_t>> prof;
+  StageTimes times;
 };
 
 namespace {
-
-struct DeaStage {
-  kg_dea_s *h;
-  const char *name;
-  hipEvent_t a = nullptr, b = nullptr;
-  DeaStage(kg_dea_s *h_, const char *n) : h(h_), name(n) {
-    if (h->profile) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, h->stream);
-    }
-  }
-  ~DeaStage() {
-    if (h->profile) {
-      (void)hipEventRecord(b, h->stream);
-      h->pending.emplace_back(name, a, b);
-    }
-  }
-};
 
 struct DeaField {
   void *dev = nullptr;
@@ -523,10 +503,7 @@ int kg_dea_destroy(kg_dea_t h) {
                   (void *)h->bestEverVars, (void *)h->currBestVars, (void *)h->maxDist, (void *)h->lb, (void *)h->ub,
                   (void *)h->ubuf, (void *)h->accept, (void *)h->sc, (void *)h->chain, (void *)h->osc})
     if (p) dev_release(p);
-  for (auto &t : h->pending) {
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
+  h->times.release();
   if (h->stream) stream_release(h->stream);
   delete h;
   return 0;
@@ -536,10 +513,10 @@ int kg_dea_initialize(kg_dea_t h) {
   KG_CHECK(h, "kg_dea_initialize: null handle");
   const size_t N = h->N, P = h->P, tot = P * N;
   {
-    DeaStage st(h, "words");
+    Stage st(h->times, h->stream, "words");
     if (h->uniform.uniforms(h->ubuf, tot, h->stream)) return 1;
   }
-  DeaStage st(h, "propose");
+  Stage st(h->times, h->stream, "propose");
   hipLaunchKernelGGL(k_dea_init, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->N, tot, h->lb, h->ub,
                      h->ubuf, h->X, h->cand);
   KG_HIP(hipGetLastError());
@@ -575,11 +552,11 @@ int kg_dea_prepare(kg_dea_t h, size_t generation) {
         return 1;
       }
       {
-        DeaStage st(h, "words");
+        Stage st(h->times, h->stream, "words");
         if (h->uniform.peek_uniforms(h->ubuf, h->window, h->stream)) return 1;
       }
       {
-        DeaStage st(h, "propose");
+        Stage st(h->times, h->stream, "propose");
         hipLaunchKernelGGL(k_dea_propose, dim3(1), dim3(DEA_TPB), 0, h->stream, h->N, h->P,
                            h->cfg.parent_rule == KG_DEA_PARENT_BEST ? 1 : 0,
                            h->cfg.mutation_rule == KG_DEA_MUTATION_SELF_ADAPTIVE ? 1 : 0, h->cfg.fix_infeasible ? 1 : 0,
@@ -617,7 +594,7 @@ int kg_dea_prepare(kg_dea_t h, size_t generation) {
 int kg_dea_eval_builtin(kg_dea_t h, int objective) {
   KG_CHECK(h, "kg_dea_eval_builtin: null handle");
   KG_CHECK(objective >= 0 && objective <= 2, "unknown builtin objective");
-  DeaStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   if (h->N <= 128)
     hipLaunchKernelGGL(k_objective2, dim3((h->P + OB2_R - 1) / OB2_R), dim3(256), ob2_lds_bytes(h->N), h->stream, h->N,
                        h->P, objective, (const double *)h->cand, h->F, h->osc, (double)h->P);
@@ -646,7 +623,7 @@ int kg_dea_set_fitness(kg_dea_t h, const double *F) {
   // Optimization::evaluate (optimization.cpp.base:32-33)
   for (int i = 0; i < h->P; i++)
     KG_CHECK(std::isfinite(F[i]), "Non finite value of function evaluation detected for sample " + std::to_string(i));
-  DeaStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   KG_HIP(hipMemcpyAsync(h->F, F, h->P * sizeof(double), hipMemcpyHostToDevice, h->stream));
   // KORALI_START of every sample (DEA.cpp.base:77); kg_cmaes.hip's kernel on the same CmaesScalars
   hipLaunchKernelGGL(k_add_evals, dim3(1), dim3(1), 0, h->stream, h->osc, (double)h->P);
@@ -659,7 +636,7 @@ int kg_dea_update(kg_dea_t h, size_t generation) {
   KG_CHECK(h, "kg_dea_update: null handle");
   KG_CHECK(h->initialized, "kg_dea_update: the handle holds no population");
   (void)generation;
-  DeaStage st(h, "update");
+  Stage st(h->times, h->stream, "update");
   const size_t tot = (size_t)h->P * h->N;
   hipLaunchKernelGGL(k_dea_select, dim3(1), dim3(DEA_TPB), 0, h->stream, h->N, h->P, h->cfg.accept_rule,
                      (const double *)h->F, (const double *)h->Fprev, (const double *)h->cand, h->mean, h->prevMean,
@@ -755,34 +732,14 @@ int kg_dea_windows(kg_dea_t h, size_t *last_windows, size_t *window_words) {
 
 int kg_dea_profile(kg_dea_t h, int enable) {
   KG_CHECK(h, "kg_dea_profile: null handle");
-  h->profile = enable != 0;
+  h->times.on = enable != 0;
   return 0;
 }
 
 int kg_dea_profile_read(kg_dea_t h, const char *stage, double *ms_total, size_t *count) {
   KG_CHECK(h, "kg_dea_profile_read: null handle");
   KG_CHECK(ms_total && count, "kg_dea_profile_read: null output");
-  KG_HIP(hipStreamSynchronize(h->stream));
-  for (auto &t : h->pending) {
-    float ms = 0.f;
-    KG_HIP(hipEventElapsedTime(&ms, std::get<1>(t), std::get<2>(t)));
-    auto &p = h->prof[std::get<0>(t)];
-    p.first += ms;
-    p.second += 1;
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  h->pending.clear();
-  auto it = h->prof.find(stage ? stage : "");
-  if (it == h->prof.end()) {
-    *ms_total = 0;
-    *count = 0;
-  } else {
-    *ms_total = it->second.first;
-    *count = it->second.second;
-    h->prof.erase(it);
-  }
-  return 0;
+  return h->times.read(h->stream, stage, ms_total, count);
 }
 
 }  // extern "C"

@@ -37,6 +37,7 @@
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
 #include "kg_gsl.hpp"
+#include "kg_profile.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -431,31 +432,10 @@ struct kg_mcmc_s {
   int nextLevel = 0;      // the level kg_mcmc_propose expects
   bool proposed = false;  // ... and whether its candidate waits for kg_mcmc_decide
   MtStream normal, uniform;
-  bool profile = false;
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, std::pair<double, size_t>> prof;
+  StageTimes times;
 };
 
 namespace {
-
-struct McStage {
-  kg_mcmc_s *h;
-  const char *name;
-  hipEvent_t a = nullptr, b = nullptr;
-  McStage(kg_mcmc_s *h_, const char *n) : h(h_), name(n) {
-    if (h->profile) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, h->stream);
-    }
-  }
-  ~McStage() {
-    if (h->profile) {
-      (void)hipEventRecord(b, h->stream);
-      h->pending.emplace_back(name, a, b);
-    }
-  }
-};
 
 McPriors mc_priors(kg_mcmc_s *h) { return McPriors{h->kind, h->pmin, h->pmax, h->cst}; }
 
@@ -520,7 +500,7 @@ bool mc_field(kg_mcmc_s *h, const char *name, McField &f) {
 
 // the windows of one launch: W candidates' normals with their block ends, W uniforms
 int mc_fill_windows(kg_mcmc_s *h, size_t W) {
-  McStage st(h, "window");
+  Stage st(h->times, h->stream, "window");
   const size_t NN = (size_t)h->N * h->N;
   if (h->normal.polar_normals(h->z, W * NN, NN, h->blockEnd, h->stream)) return 1;
   if (h->uniform.peek_uniforms(h->u, W, h->stream)) return 1;
@@ -664,10 +644,7 @@ int kg_mcmc_destroy(kg_mcmc_t h) {
                   (void *)h->db, (void *)h->dbEval, (void *)h->pmin, (void *)h->pmax, (void *)h->cst, (void *)h->kind,
                   (void *)h->z, (void *)h->u, (void *)h->blockEnd, (void *)h->al, (void *)h->run})
     if (p) dev_release(p);
-  for (auto &t : h->pending) {
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
+  h->times.release();
   if (h->stream) stream_release(h->stream);
   delete h;
   return 0;
@@ -688,7 +665,7 @@ int kg_mcmc_run(kg_mcmc_t h, size_t first_generation, size_t count, size_t max_m
     const size_t W = remaining < h->window / R ? remaining * R : h->window;
     if (mc_fill_windows(h, W)) return 1;
     {
-      McStage st(h, "chain");
+      Stage st(h->times, h->stream, "chain");
       hipLaunchKernelGGL(k_mcmc_chain, dim3(1), dim3(MC_TPB), mc_lds_bytes(h->N), h->stream, h->c, mc_priors(h),
                          (unsigned long long)(first_generation + total), (unsigned long long)remaining,
                          (double)max_model_evaluations, (unsigned long long)W, (const double *)h->z,
@@ -698,7 +675,7 @@ int kg_mcmc_run(kg_mcmc_t h, size_t first_generation, size_t count, size_t max_m
     }
     McRun r{};
     {
-      McStage st(h, "consume");
+      Stage st(h->times, h->stream, "consume");
       if (h->normal.consume_normals_dev(&h->run->usedBlocks, (size_t)h->N * h->N, h->blockEnd, h->stream)) return 1;
       if (h->uniform.consume_words_dev(&h->run->usedWords, h->stream)) return 1;
       KG_HIP(hipMemcpyAsync(&r, h->run, sizeof(r), hipMemcpyDeviceToHost, h->stream));
@@ -880,34 +857,14 @@ int kg_mcmc_diagnostics(kg_mcmc_t h, size_t *last_windows, size_t *last_relaunch
 
 int kg_mcmc_profile(kg_mcmc_t h, int enable) {
   KG_CHECK(h, "kg_mcmc_profile: null handle");
-  h->profile = enable != 0;
+  h->times.on = enable != 0;
   return 0;
 }
 
 int kg_mcmc_profile_read(kg_mcmc_t h, const char *stage, double *ms_total, size_t *count) {
   KG_CHECK(h, "kg_mcmc_profile_read: null handle");
   KG_CHECK(ms_total && count, "kg_mcmc_profile_read: null output");
-  KG_HIP(hipStreamSynchronize(h->stream));
-  for (auto &t : h->pending) {
-    float ms = 0.f;
-    KG_HIP(hipEventElapsedTime(&ms, std::get<1>(t), std::get<2>(t)));
-    auto &p = h->prof[std::get<0>(t)];
-    p.first += ms;
-    p.second += 1;
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  h->pending.clear();
-  auto it = h->prof.find(stage ? stage : "");
-  if (it == h->prof.end()) {
-    *ms_total = 0;
-    *count = 0;
-  } else {
-    *ms_total = it->second.first;
-    *count = it->second.second;
-    h->prof.erase(it);
-  }
-  return 0;
+  return h->times.read(h->stream, stage, ms_total, count);
 }
 
 }  // extern "C"

@@ -40,6 +40,7 @@
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
 #include "kg_gsl.hpp"
+#include "kg_profile.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -887,31 +888,10 @@ struct kg_mocmaes_s {
   size_t window = 0, maxWindows = 0, windowsLast = 0, roundsLast = 0;
   bool initialized = false;
   MtStream normal, uniform;
-  bool profile = false;
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, std::pair<double, size_t>> prof;
+  StageTimes times;
 };
 
 namespace {
-
-struct MoStage {
-  kg_mocmaes_s *h;
-  const char *name;
-  hipEvent_t a = nullptr, b = nullptr;
-  MoStage(kg_mocmaes_s *h_, const char *n) : h(h_), name(n) {
-    if (h->profile) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, h->stream);
-    }
-  }
-  ~MoStage() {
-    if (h->profile) {
-      (void)hipEventRecord(b, h->stream);
-      h->pending.emplace_back(name, a, b);
-    }
-  }
-};
 
 struct MoField {
   void *dev = nullptr;
@@ -1231,10 +1211,7 @@ int kg_mocmaes_destroy(kg_mocmaes_t h) {
                   (void *)h->minMax,    (void *)h->members,   (void *)h->order,     (void *)h->cand,
                   (void *)h->keep,      (void *)h->sc,        (void *)h->chain,     (void *)h->so})
     if (p) dev_release(p);
-  for (auto &t : h->pending) {
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
+  h->times.release();
   if (h->stream) stream_release(h->stream);
   delete h;
   return 0;
@@ -1283,7 +1260,7 @@ int kg_mocmaes_prepare(kg_mocmaes_t h, size_t generation) {
   if (generation == 1 && !h->initialized && kg_mocmaes_initialize(h)) return 1;
   KG_CHECK(h->initialized,
            "kg_mocmaes_prepare: the handle holds no state (kg_mocmaes_initialize, or a restored state, first)");
-  MoStage st(h, "draw");
+  Stage st(h->times, h->stream, "draw");
   const int N = h->N, P = h->P, mu = h->mu;
   h->cur = 1 - h->cur;  // Previous* = Current* (:176-181)
   const int c = h->cur;
@@ -1344,7 +1321,7 @@ int kg_mocmaes_eval_builtin(kg_mocmaes_t h, int objective) {
            "unknown builtin multi-objective kernel");
   KG_CHECK(h->K == (objective == KG_MOCMAES_OBJ_ROSENBROCK_SPHERE ? 2 : 3),
            "the builtin objective's number of objectives differs from 'Num Objectives'");
-  MoStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   hipLaunchKernelGGL(k_mo_objective, dim3((h->P + MO_TPB - 1) / MO_TPB), dim3(MO_TPB), 0, h->stream, h->N, h->P, h->K,
                      (const double *)h->X[h->cur], h->V[h->cur], h->sc);
   KG_HIP(hipGetLastError());
@@ -1370,7 +1347,7 @@ int kg_mocmaes_set_values(kg_mocmaes_t h, const double *V) {
   for (size_t e = 0; e < (size_t)h->P * h->K; e++)
     KG_CHECK(std::isfinite(V[e]), "Non finite value of function evaluation detected for sample " +
                                       std::to_string(e / h->K) + ", objective " + std::to_string(e % h->K));
-  MoStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   KG_HIP(hipMemcpyAsync(h->V[h->cur], V, (size_t)h->P * h->K * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_mo_add_evals, dim3(1), dim3(1), 0, h->stream, h->sc, (double)h->P);
   KG_HIP(hipGetLastError());
@@ -1384,11 +1361,11 @@ int kg_mocmaes_update(kg_mocmaes_t h, size_t generation) {
   (void)generation;
   const int c = h->cur, p = 1 - h->cur;
   {
-    MoStage st(h, "sort");
+    Stage st(h->times, h->stream, "sort");
     if (mo_sort(h)) return 1;
   }
   {
-    MoStage st(h, "update");
+    Stage st(h->times, h->stream, "update");
     hipLaunchKernelGGL(k_mo_update, dim3(h->P), dim3(MO_TPB), 0, h->stream, h->c, (const int *)h->order,
                        (const double *)h->parentIdx, (const double *)h->X[c], (const double *)h->pX,
                        (const double *)h->pSg, (const double *)h->pC, (const double *)h->pPa, (const double *)h->pSr,
@@ -1396,7 +1373,7 @@ int kg_mocmaes_update(kg_mocmaes_t h, size_t generation) {
     KG_HIP(hipGetLastError());
   }
   {
-    MoStage st(h, "parents");
+    Stage st(h->times, h->stream, "parents");
     hipLaunchKernelGGL(k_mo_gather, dim3(2 * h->P), dim3(MO_TPB), 0, h->stream, h->c,
                        h->cfg.parent_order == KG_MOCMAES_PARENTS_RECORDED ? 1 : 0, (const int *)h->order,
                        (const double *)h->X[c], (const double *)h->X[p], (const double *)h->Sg[c],
@@ -1405,7 +1382,7 @@ int kg_mocmaes_update(kg_mocmaes_t h, size_t generation) {
                        (const double *)h->Sr[p], h->pX, h->pSg, h->pC, h->pPa, h->pSr);
     KG_HIP(hipGetLastError());
   }
-  MoStage st(h, "statistics");
+  Stage st(h->times, h->stream, "statistics");
   return mo_statistics(h);
 }
 
@@ -1502,34 +1479,14 @@ int kg_mocmaes_diagnostics(kg_mocmaes_t h, size_t *last_windows, size_t *window_
 
 int kg_mocmaes_profile(kg_mocmaes_t h, int enable) {
   KG_CHECK(h, "kg_mocmaes_profile: null handle");
-  h->profile = enable != 0;
+  h->times.on = enable != 0;
   return 0;
 }
 
 int kg_mocmaes_profile_read(kg_mocmaes_t h, const char *stage, double *ms_total, size_t *count) {
   KG_CHECK(h, "kg_mocmaes_profile_read: null handle");
   KG_CHECK(ms_total && count, "kg_mocmaes_profile_read: null output");
-  KG_HIP(hipStreamSynchronize(h->stream));
-  for (auto &t : h->pending) {
-    float ms = 0.f;
-    KG_HIP(hipEventElapsedTime(&ms, std::get<1>(t), std::get<2>(t)));
-    auto &p = h->prof[std::get<0>(t)];
-    p.first += ms;
-    p.second += 1;
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  h->pending.clear();
-  auto it = h->prof.find(stage ? stage : "");
-  if (it == h->prof.end()) {
-    *ms_total = 0;
-    *count = 0;
-  } else {
-    *ms_total = it->second.first;
-    *count = it->second.second;
-    h->prof.erase(it);
-  }
-  return 0;
+  return h->times.read(h->stream, stage, ms_total, count);
 }
 
 }  // extern "C"

@@ -38,6 +38,7 @@
 #include "../../include/korali_amd.h"
 #include "kg_common.hpp"
 #include "kg_gsl.hpp"
+#include "kg_profile.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -552,31 +553,10 @@ struct kg_nested_s {
   bool pendingLive = false;  // the pending rows are the live set (generation 1)
   bool started = false;  // the first generation ran (or a state was restored)
   bool acceptedLast = true;
-  bool profile = false;
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, std::pair<double, size_t>> prof;
+  StageTimes times;
 };
 
 namespace {
-
-struct NsStage {
-  kg_nested_s *h;
-  const char *name;
-  hipEvent_t a = nullptr, b = nullptr;
-  NsStage(kg_nested_s *h_, const char *n) : h(h_), name(n) {
-    if (h->profile) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, h->stream);
-    }
-  }
-  ~NsStage() {
-    if (h->profile) {
-      (void)hipEventRecord(b, h->stream);
-      h->pending.emplace_back(name, a, b);
-    }
-  }
-};
 
 // auxiliar/math.hpp:165-196
 double ns_safe_log_plus(double x, double y) {
@@ -759,7 +739,7 @@ int ns_update_bounds(kg_nested_s *h) {
   // (:255: the Box method holds no ellipse, so it updates on every call)
   if (h->ellipse && h->generatedSamples < h->nextUpdate) return 0;
   h->nextUpdate += (double)h->cfg.proposal_update_frequency;
-  NsStage st(h, "bounds");
+  Stage st(h->times, h->stream, "bounds");
   const int N = h->N, L = h->L;
   if (!h->ellipse) {
     hipLaunchKernelGGL(k_ns_box, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, L, (const double *)h->live, h->boxLo,
@@ -783,7 +763,7 @@ int ns_update_bounds(kg_nested_s *h) {
 
 // generateCandidates (:402-443)
 int ns_draw(kg_nested_s *h) {
-  NsStage st(h, "draw");
+  Stage st(h->times, h->stream, "draw");
   const int N = h->N, B = h->B;
   KG_HIP(hipMemsetAsync(h->chain, 0, sizeof(NsChain), h->stream));
   h->windowsLast = 0;
@@ -833,7 +813,7 @@ int ns_draw(kg_nested_s *h) {
 }
 
 int ns_evaluate_rows(kg_nested_s *h, const double *X, size_t n, double *LL, double *LP, double *LPW) {
-  NsStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   hipLaunchKernelGGL(k_ns_evaluate, dim3((unsigned)((n + NS_TPB - 1) / NS_TPB)), dim3(NS_TPB), 0, h->stream, h->N,
                      (int)n, h->cfg.likelihood, X, (const double *)h->lower, (const double *)h->width,
                      (const double *)h->logWidth, (const double *)h->pmin, (const double *)h->pmax,
@@ -980,10 +960,7 @@ int kg_nested_destroy(kg_nested_t h) {
                   (void *)h->lstar,   (void *)h->tmp,     (void *)h->flag,     (void *)h->blockEnd, (void *)h->sel,
                   (void *)h->chain})
     if (p) dev_release(p);
-  for (auto &t : h->pending) {
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
+  h->times.release();
   if (h->stream) stream_release(h->stream);
   delete h;
   return 0;
@@ -996,7 +973,7 @@ int kg_nested_prepare(kg_nested_t h, size_t generation) {
   if (generation == 1) {
     // runFirstGeneration's draws (:208-210) and the priors of the live set
     {
-      NsStage st(h, "draw");
+      Stage st(h->times, h->stream, "draw");
       if (h->uniform.uniforms(h->live, L * N, h->stream)) return 1;
     }
     if (ns_evaluate_rows(h, h->live, L, h->liveLL, h->liveLP, h->liveLPW)) return 1;
@@ -1037,7 +1014,7 @@ int kg_nested_set_evaluations(kg_nested_t h, const double *loglik) {
   const size_t n = h->pendingRows;
   for (size_t i = 0; i < n; i++)  // bayesian.cpp.base:73
     KG_CHECK(!std::isnan(loglik[i]), "Sample " + std::to_string(i) + " returned NaN logLikelihood evaluation.\n");
-  NsStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   double *LL = h->pendingLive ? h->liveLL : h->candLL;
   const double *LP = LL == h->liveLL ? h->liveLP : h->candLP;
   KG_HIP(hipMemcpyAsync(LL, loglik, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1065,7 +1042,7 @@ int kg_nested_process(kg_nested_t h, size_t generation, int *accepted, int *term
     h->pendingLive = false;
     h->modelEvaluationCount += L;
     h->generatedSamples += L;
-    NsStage st(h, "select");
+    Stage st(h->times, h->stream, "select");
     KG_HIP(hipMemsetAsync(h->cur, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_ns_sort, dim3((L + NS_TPB - 1) / NS_TPB), dim3(NS_TPB), 0, h->stream, L,
                        (const double *)h->liveLPW, (const double *)h->liveLL, h->rank[0]);
@@ -1088,7 +1065,7 @@ int kg_nested_process(kg_nested_t h, size_t generation, int *accepted, int *term
   h->generatedSamples += B;
   h->lastAccepted += 1;  // :199
   {
-    NsStage st(h, "select");
+    Stage st(h->times, h->stream, "select");
     hipLaunchKernelGGL(k_ns_select, dim3(1), dim3(NS_TPB), 0, h->stream, N, L, B, h->live, h->liveLL, h->liveLP,
                        h->liveLPW, (const double *)h->cand, (const double *)h->candLL, (const double *)h->candLP,
                        (const double *)h->candLPW, h->rank[0], h->rank[1], h->cur, h->lstar, h->out);
@@ -1360,34 +1337,14 @@ int kg_nested_diagnostics(kg_nested_t h, size_t *last_windows, size_t *last_trie
 
 int kg_nested_profile(kg_nested_t h, int enable) {
   KG_CHECK(h, "kg_nested_profile: null handle");
-  h->profile = enable != 0;
+  h->times.on = enable != 0;
   return 0;
 }
 
 int kg_nested_profile_read(kg_nested_t h, const char *stage, double *ms_total, size_t *count) {
   KG_CHECK(h, "kg_nested_profile_read: null handle");
   KG_CHECK(ms_total && count, "kg_nested_profile_read: null output");
-  KG_HIP(hipStreamSynchronize(h->stream));
-  for (auto &t : h->pending) {
-    float ms = 0.f;
-    KG_HIP(hipEventElapsedTime(&ms, std::get<1>(t), std::get<2>(t)));
-    auto &p = h->prof[std::get<0>(t)];
-    p.first += ms;
-    p.second += 1;
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  h->pending.clear();
-  auto it = h->prof.find(stage ? stage : "");
-  if (it == h->prof.end()) {
-    *ms_total = 0;
-    *count = 0;
-  } else {
-    *ms_total = it->second.first;
-    *count = it->second.second;
-    h->prof.erase(it);
-  }
-  return 0;
+  return h->times.read(h->stream, stage, ms_total, count);
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@
 //   exact GSL state (mt[624], mti) for export.
 #pragma once
 
+#include <cstring>
+
 #include "kg_common.hpp"
 
 namespace kg {
@@ -32,6 +34,20 @@ constexpr int MT_SEQ = MT_N + MT_L - 1;          // words a jump reads (20560)
 int mt_poly_degree();
 int mt_jump_poly_pow2(int e, uint64_t *out);     // x^(2^e) mod P
 int mt_jump_host(const uint32_t *window, unsigned long long J, uint32_t *out);
+
+// gsl_rng_set(mt19937, seed) in the 5000-byte layout of import_gsl /
+// export_gsl: mt[624] as 64-bit words, then mti (host)
+inline void gsl_seed_state(uint64_t seed, unsigned char *out5000) {
+  uint64_t mt[624];
+  uint64_t s = seed & 0xffffffffULL;
+  if (s == 0) s = 4357;
+  mt[0] = s;
+  for (int i = 1; i < 624; i++) mt[i] = (1812433253ULL * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint64_t)i) & 0xffffffffULL;
+  memset(out5000, 0, 5000);
+  memcpy(out5000, mt, sizeof(mt));
+  int32_t mti = 624;
+  memcpy(out5000 + 624 * 8, &mti, 4);
+}
 
 // chunked parallel production: chunk c = words [cW, (c+1)W) of the stream
 // (positions relative to the import point), made by its own workgroup from

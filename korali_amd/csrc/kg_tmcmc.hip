@@ -38,6 +38,7 @@
 #include "kg_common.hpp"
 #include "kg_gsl.hpp"
 #include "kg_mtmcmc.hpp"
+#include "kg_profile.hpp"
 #include "kg_rng.hpp"
 
 namespace kg {
@@ -1950,58 +1951,10 @@ struct kg_tmcmc_s {
   hier::Layout *hier = nullptr;
   bool prepared = false;
   // profiling
-  bool profile = false;
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, std::pair<double, size_t>> prof;
+  StageTimes times;
 };
 
 namespace {
-
-struct TmStage {
-  kg_tmcmc_s *h;
-  std::string name;
-  hipEvent_t a = nullptr, b = nullptr;
-  TmStage(kg_tmcmc_s *h_, const char *n) : h(h_), name(n) {
-    if (h->profile) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, h->stream);
-    }
-  }
-  ~TmStage() {
-    if (h->profile) {
-      (void)hipEventRecord(b, h->stream);
-      h->pending.emplace_back(name, a, b);
-    }
-  }
-};
-
-struct HostClock {
-  kg_tmcmc_s *h;
-  const char *name;
-  std::chrono::steady_clock::time_point t0;
-  HostClock(kg_tmcmc_s *h_, const char *n) : h(h_), name(n), t0(std::chrono::steady_clock::now()) {}
-  ~HostClock() {
-    if (!h->profile) return;
-    auto &p = h->prof[name];
-    p.first += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    p.second += 1;
-  }
-};
-
-template <typename T>
-int tdalloc(T **p, size_t n) {
-  if (n == 0) n = 1;
-  KG_HIP(dev_alloc(p, n * sizeof(T)));
-  if (zero_fill(*p, n * sizeof(T))) return 1;
-  return 0;
-}
-
-void seed_state(uint64_t seed, unsigned char *out5000) {
-  HostMt m;
-  m.seed(seed);
-  m.save(out5000);
-}
 
 inline unsigned nblk(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
@@ -2501,7 +2454,7 @@ int tm_ensure(T **p, size_t &cap, size_t n) {
   }
   *p = nullptr;
   cap = 0;
-  if (tdalloc(p, n)) return 1;
+  if (dalloc(p, n)) return 1;
   cap = n;
   return 0;
 }
@@ -2560,7 +2513,7 @@ int tm_schedule(kg_tmcmc_s *h) {
   const size_t M = z * (size_t)h->N;
   if (M) {
     if (tm_ensure(&h->Zx, h->capZx, std::max<size_t>(1, (zend - h->zbase) * h->N))) return 1;
-    TmStage st(h, "rng_polar");
+    Stage st(h->times, h->stream, "rng_polar");
     if (h->multivariate.polar_normals(h->Zx, M, h->N, nullptr, h->stream, h->zbase * h->N, zend * h->N)) return 1;
     if (h->multivariate.consume_normals(M, h->N, nullptr, h->stream)) return 1;
   }
@@ -2777,30 +2730,30 @@ int kg_tmcmc_create(const kg_tmcmc_cfg *cfg, kg_tmcmc_t *out) {
   }
   const size_t PN = (size_t)P * N;
   int rc = 0;
-  rc |= tdalloc(&h->leaders, PN) | tdalloc(&h->leadLL, P) | tdalloc(&h->leadLP, P) | tdalloc(&h->cand, PN);
-  rc |= tdalloc(&h->candLL, P) | tdalloc(&h->candLP, P) | tdalloc(&h->chainLen, P) | tdalloc(&h->mean, N);
-  rc |= tdalloc(&h->cov, (size_t)N * N) | tdalloc(&h->chol, (size_t)N * N) | tdalloc(&h->db, PN);
-  rc |= tdalloc(&h->dbLL, P) | tdalloc(&h->dbLP, P) | tdalloc(&h->numSel, P) | tdalloc(&h->pmin, N);
-  rc |= tdalloc(&h->pmax, N) | tdalloc(&h->negLogWidth, N) | tdalloc(&h->Z, PN) | tdalloc(&h->U, P);
+  rc |= dalloc(&h->leaders, PN) | dalloc(&h->leadLL, P) | dalloc(&h->leadLP, P) | dalloc(&h->cand, PN);
+  rc |= dalloc(&h->candLL, P) | dalloc(&h->candLP, P) | dalloc(&h->chainLen, P) | dalloc(&h->mean, N);
+  rc |= dalloc(&h->cov, (size_t)N * N) | dalloc(&h->chol, (size_t)N * N) | dalloc(&h->db, PN);
+  rc |= dalloc(&h->dbLL, P) | dalloc(&h->dbLP, P) | dalloc(&h->numSel, P) | dalloc(&h->pmin, N);
+  rc |= dalloc(&h->pmax, N) | dalloc(&h->negLogWidth, N) | dalloc(&h->Z, PN) | dalloc(&h->U, P);
   h->capU = P;
-  rc |= tdalloc(&h->Uprior, PN) | tdalloc(&h->E, (size_t)(CV_MAX_PTS + 1) * P) | tdalloc(&h->w, P);
-  rc |= tdalloc(&h->uoff, N) | tdalloc(&h->ustride, N) | tdalloc(&h->src, P) | tdalloc(&h->acc, P);
-  rc |= tdalloc(&h->vkind, N);
+  rc |= dalloc(&h->Uprior, PN) | dalloc(&h->E, (size_t)(CV_MAX_PTS + 1) * P) | dalloc(&h->w, P);
+  rc |= dalloc(&h->uoff, N) | dalloc(&h->ustride, N) | dalloc(&h->src, P) | dalloc(&h->acc, P);
+  rc |= dalloc(&h->vkind, N);
   for (int k : h->hkind)
     if (k) {
-      rc |= tdalloc(&h->priorNrm, PN);
+      rc |= dalloc(&h->priorNrm, PN);
       break;
     }
-  rc |= tdalloc(&h->pend, P) | tdalloc(&h->sch, P) | tdalloc(&h->dLen, P);
+  rc |= dalloc(&h->pend, P) | dalloc(&h->sch, P) | dalloc(&h->dLen, P);
   h->xchWords = 3 * (PN + 2 * (size_t)P) + h->world;
-  if (cfg->shard_count >= 1) rc |= tdalloc(&h->xch, h->xchWords);  // explicitly sharded (even one rank)
-  rc |= tdalloc(&h->dev, 1) | tdalloc(&h->pairs, N * (N + 1) / 2);
+  if (cfg->shard_count >= 1) rc |= dalloc(&h->xch, h->xchWords);  // explicitly sharded (even one rank)
+  rc |= dalloc(&h->dev, 1) | dalloc(&h->pairs, N * (N + 1) / 2);
   {  // (LDS form: P x N + 2; row form: N x wr_pitch(P))
     const size_t nf = std::max(PN + 2, (size_t)N * wr_pitch(P));
-    rc |= tdalloc(&h->fA, nf) | tdalloc(&h->fB, nf);
+    rc |= dalloc(&h->fA, nf) | dalloc(&h->fB, nf);
   }
-  rc |= tdalloc((char **)&h->cvPart, (CV_MAX_PTS + 1) * CV_BLOCKS * sizeof(CvPart));
-  rc |= tdalloc((char **)&h->dNm, sizeof(NmOut)) | tdalloc((char **)&h->nmSync, sizeof(NmSync));
+  rc |= dalloc((char **)&h->cvPart, (CV_MAX_PTS + 1) * CV_BLOCKS * sizeof(CvPart));
+  rc |= dalloc((char **)&h->dNm, sizeof(NmOut)) | dalloc((char **)&h->nmSync, sizeof(NmSync));
   if (rc) {
     delete h;
     return 1;
@@ -2870,16 +2823,16 @@ int kg_tmcmc_create(const kg_tmcmc_cfg *cfg, kg_tmcmc_t *out) {
     return 1;
   }
   unsigned char st[5000];
-  seed_state(cfg->multivariate_seed, st);
+  gsl_seed_state(cfg->multivariate_seed, st);
   if (h->multivariate.import_gsl(st, h->stream)) return 1;
-  seed_state(cfg->uniform_seed, st);
+  gsl_seed_state(cfg->uniform_seed, st);
   if (h->uniform.import_gsl(st, h->stream)) return 1;
   h->multinomialRng.seed(cfg->multinomial_seed);
   h->priorRng.resize(nd);
   for (int k = 0; k < nd; k++) {
     h->priorRng[k] = new MtStream();
     if (h->priorRng[k]->init((h->distKind[k] ? 1 : 2 * h->distVars[k] * (size_t)P) + 4096)) return 1;
-    seed_state(cfg->prior_seeds ? cfg->prior_seeds[k] : 0, st);
+    gsl_seed_state(cfg->prior_seeds ? cfg->prior_seeds[k] : 0, st);
     if (h->priorRng[k]->import_gsl(st, h->stream)) return 1;
   }
   h->chainCount = P;
@@ -2908,7 +2861,7 @@ int kg_tmcmc_create(const kg_tmcmc_cfg *cfg, kg_tmcmc_t *out) {
     h->mtLead.assign(PN, 0.0);
     h->mtExtra.assign(P, 0.0);
     h->mtMode.assign(P, 0);
-    if (tdalloc(&h->mtExtraDev, P) || tdalloc(&h->mtModeDev, P)) return 1;
+    if (dalloc(&h->mtExtraDev, P) || dalloc(&h->mtModeDev, P)) return 1;
   }
   *out = h;
   return 0;
@@ -2937,10 +2890,7 @@ int kg_tmcmc_destroy(kg_tmcmc_t h) {
     delete h->hier;
   }
   for (auto *r : h->priorRng) delete r;
-  for (auto &t : h->pending) {
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
+  h->times.release();
   stream_release(h->stream);
   delete h;
   return 0;
@@ -2972,7 +2922,7 @@ static int tm_mt_candidates(kg_tmcmc_s *h) {
     if (draws[c]) M += N;
   }
   if (M) {
-    TmStage st(h, "rng_polar");
+    Stage st(h->times, h->stream, "rng_polar");
     if (h->multivariate.polar_normals(h->Z, M, N, nullptr, h->stream)) return 1;
     if (h->multivariate.consume_normals(M, N, nullptr, h->stream)) return 1;
     if (h->multivariate.prefetch(PN, h->stream)) return 1;
@@ -2980,7 +2930,7 @@ static int tm_mt_candidates(kg_tmcmc_s *h) {
     KG_HIP(hipMemcpyAsync(z.data(), h->Z, M * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   KG_HIP(hipStreamSynchronize(h->stream));
-  TmStage st(h, "draw");
+  Stage st(h->times, h->stream, "draw");
   size_t k = 0;
   const double alpha = 0.5 * h->cfg.step_size;
   for (int c = 0; c < P; c++) {
@@ -3113,7 +3063,7 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
   KG_HIP(hipMemsetAsync(h->dev, 0, sizeof(TmDev), h->stream));
   if (generation > 1 && h->multivariate.prefetch(PN, h->stream)) return 1;
   {
-    TmStage st(h, "cholesky");
+    Stage st(h->times, h->stream, "cholesky");
     hipLaunchKernelGGL(k_tm_cholesky, dim3(1), dim3(256), (size_t)N * (N + 1) * sizeof(double), h->stream, N, h->cov,
                        h->chol, h->dev);
     KG_HIP(hipGetLastError());
@@ -3132,7 +3082,7 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
     KG_HIP(hipMemsetAsync(h->mtModeDev, 0, (size_t)P, h->stream));
   }
   if (generation == 1) {
-    TmStage st(h, "prior_draw");
+    Stage st(h->times, h->stream, "prior_draw");
     if (h->priorNrm && tm_normal_priors(h)) return 1;
     for (int k = 0; k < h->ndist; k++)
       if (h->distVars[k] && !h->distKind[k] &&
@@ -3145,7 +3095,7 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
     if (tm_mt_candidates(h)) return 1;
   } else {
     {
-      TmStage st(h, "rng_polar");
+      Stage st(h->times, h->stream, "rng_polar");
       if (h->zAhead && h->world == 1) {  // formed during the last generation's multinomial (joined above)
       } else if (h->multivariate.polar_normals(h->Z, PN, N, nullptr, h->stream, h->ca * N, h->cbp * N)) {
         return 1;
@@ -3156,7 +3106,7 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
       // this generation's search runs on the host
       if (h->multivariate.prefetch(PN, h->stream)) return 1;
     }
-    TmStage st(h, "draw");
+    Stage st(h->times, h->stream, "draw");
     const int CB = std::max(1, 256 / N);
     const size_t lbytes = (size_t)N * (N + 1) * sizeof(double) + (size_t)CB * N * sizeof(double);
     if (h->cbp > h->ca)
@@ -3176,7 +3126,7 @@ int kg_tmcmc_prepare(kg_tmcmc_t h, size_t generation) {
 }
 
 int kg_tmcmc_evaluate(kg_tmcmc_t h) {
-  TmStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   // a hierarchical handle: the log-priors (and -inf log-likelihoods below a
   // -inf prior) here, the likelihood of the other pending chains after it;
   // Theta: the sub-problem's builtin log-likelihood here, completed after it
@@ -3186,7 +3136,7 @@ int kg_tmcmc_evaluate(kg_tmcmc_t h) {
                      h->candLL, h->candLP, h->pend);
   KG_HIP(hipGetLastError());
   if (h->hier) {
-    TmStage sh(h, "hier_loglik");
+    Stage sh(h->times, h->stream, "hier_loglik");
     if (theta && tm_theta_join(h)) return 1;
     return hier::evaluate(*h->hier, h->cand, (size_t)h->N, (size_t)h->P, h->pend, h->candLP, theta ? h->candLL : nullptr,
                           h->candLL, h->stream);
@@ -3262,9 +3212,9 @@ int kg_tmcmc_set_hierarchical(kg_tmcmc_t h, const kg_tmcmc_hierarchical *d) {
   L->R = R;
   const size_t DR = (size_t)D * R;
   double *rowsDev = nullptr;
-  int rc = tdalloc(&L->kind, D) | tdalloc(&L->psrc, 2 * D) | tdalloc(&L->pconst, 2 * D) |
-           tdalloc(&L->goff, goff.size()) | tdalloc(&L->A, DR) | tdalloc(&L->B, DR) | tdalloc(&L->Cn, psi ? 1 : DR) |
-           tdalloc(&L->base, psi ? R : 1) | tdalloc(&L->status, 1) | tdalloc(&rowsDev, R * W);
+  int rc = dalloc(&L->kind, D) | dalloc(&L->psrc, 2 * D) | dalloc(&L->pconst, 2 * D) |
+           dalloc(&L->goff, goff.size()) | dalloc(&L->A, DR) | dalloc(&L->B, DR) | dalloc(&L->Cn, psi ? 1 : DR) |
+           dalloc(&L->base, psi ? R : 1) | dalloc(&L->status, 1) | dalloc(&rowsDev, R * W);
   if (rc) {
     if (rowsDev) dev_release(rowsDev);
     return 1;
@@ -3362,10 +3312,10 @@ int kg_tmcmc_set_hierarchical_theta(kg_tmcmc_t h, const kg_tmcmc_hier_theta *d) 
     }
   } scratch{{(void **)&psiDev, (void **)&subDev, (void **)&S, (void **)&logS, (void **)&lpS, (void **)&part,
              (void **)&goffK}};
-  if (tdalloc(&L->kind, D) | tdalloc(&L->psrc, 2 * D) | tdalloc(&L->pconst, 2 * D) | tdalloc(&L->goff, 2) |
-      tdalloc(&L->A, DM) | tdalloc(&L->B, DM) | tdalloc(&L->Cn, DM) | tdalloc(&L->base, 2) | tdalloc(&L->den, M) |
-      tdalloc(&L->status, 1) | tdalloc(&psiDev, M * W) | tdalloc(&subDev, DK) | tdalloc(&S, DK) | tdalloc(&logS, DK) |
-      tdalloc(&lpS, K) | tdalloc(&part, M) | tdalloc(&goffK, 2))
+  if (dalloc(&L->kind, D) | dalloc(&L->psrc, 2 * D) | dalloc(&L->pconst, 2 * D) | dalloc(&L->goff, 2) |
+      dalloc(&L->A, DM) | dalloc(&L->B, DM) | dalloc(&L->Cn, DM) | dalloc(&L->base, 2) | dalloc(&L->den, M) |
+      dalloc(&L->status, 1) | dalloc(&psiDev, M * W) | dalloc(&subDev, DK) | dalloc(&S, DK) | dalloc(&logS, DK) |
+      dalloc(&lpS, K) | dalloc(&part, M) | dalloc(&goffK, 2))
     return 1;
   KG_HIP(host_alloc(&L->hStatus, sizeof(unsigned long long), hipHostMallocDefault));
   *L->hStatus = hier::ST_CLEAR;
@@ -3396,7 +3346,7 @@ int kg_tmcmc_set_hierarchical_theta(kg_tmcmc_t h, const kg_tmcmc_hier_theta *d) 
   KG_HIP(hipStreamSynchronize(h->stream));
   L->negLogM = negLog[0];
   {
-    TmStage st(h, "theta_denominators");
+    Stage st(h->times, h->stream, "theta_denominators");
     if (hier::denominators(*L, K, S, logS, lpS, goffK, negLog[1], part, h->stream)) return 1;
   }
   KG_HIP(hipStreamSynchronize(h->stream));
@@ -3439,7 +3389,7 @@ int kg_tmcmc_theta_loglik(kg_tmcmc_t h, const double *X, size_t rows, const doub
 }
 
 int kg_tmcmc_evaluate_prior(kg_tmcmc_t h) {
-  TmStage st(h, "evaluate");
+  Stage st(h->times, h->stream, "evaluate");
   hipLaunchKernelGGL(k_tm_evaluate, dim3(nblk(h->P, 128)), dim3(128), 0, h->stream, h->N, h->P, -1, h->cand,
                      h->negLogWidth, h->pmin, h->pmax, h->vkind, h->candLL, h->candLP, h->pend);
   KG_HIP(hipGetLastError());
@@ -3600,7 +3550,7 @@ int kg_tmcmc_advance(kg_tmcmc_t h, size_t generation, size_t *pending) {
   }
   if (!h->rounds) {
     // every chain runs one step: Uniform c, database entry c
-    TmStage st(h, "accept");
+    Stage st(h->times, h->stream, "accept");
     if (h->uniform.uniforms(h->U, P, h->stream)) return 1;
     const int a = (int)h->ca, b = (int)h->cb;
     if (b > a) {
@@ -3635,7 +3585,7 @@ int kg_tmcmc_advance(kg_tmcmc_t h, size_t generation, size_t *pending) {
   } else {
     const int a = (int)h->ca, b = (int)h->cb, B = (int)h->currentBurnIn;
     if (b > a) {
-      TmStage st(h, "accept");
+      Stage st(h->times, h->stream, "accept");
       hipLaunchKernelGGL(k_tm_round_accept, dim3(nblk(b - a, 256)), dim3(256), 0, h->stream, a, b, s, B,
                          generation == 1 ? 1 : 0, h->annealingExponent, h->sch, h->U, h->candLL, h->candLP,
                          h->leadLL, h->leadLP, h->dbLL, h->dbLP, h->acc, h->dev);
@@ -3650,7 +3600,7 @@ int kg_tmcmc_advance(kg_tmcmc_t h, size_t generation, size_t *pending) {
         mine += (c >= a && c < b);
       }
     if (mine) {
-      TmStage st(h, "draw");
+      Stage st(h->times, h->stream, "draw");
       const int CB = std::max(1, 256 / N);
       const size_t lbytes = (size_t)N * (N + 1) * sizeof(double) + (size_t)CB * N * sizeof(double);
       hipLaunchKernelGGL(k_tm_draw<true>, dim3(nblk(b - a, CB)), dim3(256), lbytes, h->stream, N, a, b, h->Zx,
@@ -3698,7 +3648,7 @@ int kg_tmcmc_process_finalize(kg_tmcmc_t h, size_t generation) {
     KG_HIP(hipGetLastError());
   }
   {
-    TmStage st(h, "accept");
+    Stage st(h->times, h->stream, "accept");
     hipLaunchKernelGGL(k_tm_max, dim3(1), dim3(1024), 0, h->stream, P, h->dbLL, 1.0, 0, &h->dev->llmaxCv,
                        &h->dev->maxLoglikelihood);
     KG_HIP(hipGetLastError());
@@ -3710,7 +3660,7 @@ int kg_tmcmc_process_finalize(kg_tmcmc_t h, size_t generation) {
   double xmin = 0, fmin = 0;
   size_t iters = 0;
   {
-    HostClock hc(h, "min_search");
+    HostStage hc(h->times, "min_search");
     const bool onHost = h->exactSearch || h->hostSearch;
     if ((onHost ? min_search : min_search_device)(h, h->annealingExponent, h->cfg.target_cov, xmin, fmin, iters))
       return 1;
@@ -3744,7 +3694,7 @@ int kg_tmcmc_process_finalize(kg_tmcmc_t h, size_t generation) {
   }
   const double drho = h->annealingExponent - h->previousAnnealingExponent;
   {
-    TmStage st(h, "weights");
+    Stage st(h->times, h->stream, "weights");
     hipLaunchKernelGGL(k_tm_max, dim3(1), dim3(1024), 0, h->stream, P, h->dbLL, drho, 1, &h->dev->lwmax,
                        (double *)nullptr);
     hipLaunchKernelGGL(k_tm_lw_exp, dim3(nblk(P, 256)), dim3(256), 0, h->stream, P, h->dbLL, drho, h->dev, h->E);
@@ -3764,7 +3714,7 @@ int kg_tmcmc_process_finalize(kg_tmcmc_t h, size_t generation) {
   size_t zeroCount = 0, leaderId = 0, total = 0;
   double sumw2 = 0.0;
   {
-    HostClock hc(h, "multinomial");
+    HostStage hc(h->times, "multinomial");
     double *wt = h->hW;
     const double lwmax = h->hDev->lwmax;
     double sw = 0.0;
@@ -3824,7 +3774,7 @@ int kg_tmcmc_process_finalize(kg_tmcmc_t h, size_t generation) {
   KG_HIP(hipMemcpyAsync(h->src, h->hSrc, leaderId * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
   KG_HIP(hipMemcpyAsync(h->dLen, h->hLenD, leaderId * sizeof(double), hipMemcpyHostToDevice, h->stream));
   {
-    TmStage st(h, "mean_cov");
+    Stage st(h->times, h->stream, "mean_cov");
     const int npairs = N * (N + 1) / 2;
     if (h->wsumLds) {
       hipLaunchKernelGGL(k_tm_factors_mean, dim3(nblk(PN, 256)), dim3(256), 0, h->stream, N, P, h->db, h->w, h->fA);
@@ -3850,7 +3800,7 @@ int kg_tmcmc_process_finalize(kg_tmcmc_t h, size_t generation) {
     KG_HIP(hipGetLastError());
   }
   {
-    TmStage st(h, "expand");
+    Stage st(h->times, h->stream, "expand");
     hipLaunchKernelGGL(k_tm_expand, dim3(nblk(PN, 256)), dim3(256), 0, h->stream, N, P, (int)leaderId, h->src,
                        h->dLen, h->db, h->dbLL, h->dbLP, h->leaders, h->leadLL, h->leadLP, h->chainLen);
     KG_HIP(hipGetLastError());
@@ -3965,32 +3915,15 @@ int kg_tmcmc_stream(kg_tmcmc_t h, void **stream) {
 }
 
 int kg_tmcmc_profile(kg_tmcmc_t h, int enable) {
-  h->profile = enable != 0;
+  KG_CHECK(h, "kg_tmcmc_profile: null handle");
+  h->times.on = enable != 0;
   return 0;
 }
 
 int kg_tmcmc_profile_read(kg_tmcmc_t h, const char *stage, double *ms_total, size_t *count) {
-  KG_HIP(hipStreamSynchronize(h->stream));
-  for (auto &t : h->pending) {
-    float ms = 0.f;
-    KG_HIP(hipEventElapsedTime(&ms, std::get<1>(t), std::get<2>(t)));
-    auto &p = h->prof[std::get<0>(t)];
-    p.first += ms;
-    p.second += 1;
-    (void)hipEventDestroy(std::get<1>(t));
-    (void)hipEventDestroy(std::get<2>(t));
-  }
-  h->pending.clear();
-  auto it = h->prof.find(stage);
-  if (it == h->prof.end()) {
-    *ms_total = 0;
-    *count = 0;
-  } else {
-    *ms_total = it->second.first;
-    *count = it->second.second;
-    h->prof.erase(it);
-  }
-  return 0;
+  KG_CHECK(h, "kg_tmcmc_profile_read: null handle");
+  KG_CHECK(ms_total && count, "kg_tmcmc_profile_read: null output");
+  return h->times.read(h->stream, stage, ms_total, count);
 }
 
 }  // extern "C"

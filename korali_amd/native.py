@@ -221,6 +221,15 @@ def lib():
         L.kg_last_error.restype = cp
         L.kg_abi_version.restype = ip
         L.kg_device_count.argtypes = [C.POINTER(C.c_int)]
+        # the entries every solver handle has (class _Handle)
+        for p in ("kg_cmaes", "kg_dea", "kg_mocmaes", "kg_nested", "kg_mcmc", "kg_tmcmc"):
+            getattr(L, p + "_field_size").argtypes = [vp, cp, C.POINTER(sz)]
+            getattr(L, p + "_get_field").argtypes = [vp, cp, dp, sz]
+            getattr(L, p + "_set_field").argtypes = [vp, cp, dp, sz]
+            getattr(L, p + "_get_rng").argtypes = [vp, ip, vp]
+            getattr(L, p + "_set_rng").argtypes = [vp, ip, vp]
+            getattr(L, p + "_profile").argtypes = [vp, ip]
+            getattr(L, p + "_profile_read").argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_cmaes_create.argtypes = [C.POINTER(_CmaesCfg), C.POINTER(vp)]
         for f in ("kg_cmaes_destroy", "kg_cmaes_initialize", "kg_cmaes_sample", "kg_cmaes_synchronize",
                   "kg_cmaes_begin_sample"):
@@ -261,21 +270,14 @@ def lib():
         L.kg_debug_mt_export_gsl.argtypes = [vp, vp]
         L.kg_debug_mt_state.argtypes = [vp, vp, C.POINTER(C.c_ulonglong)]
         L.kg_cmaes_generation.argtypes = [vp, sz, ip]
-        L.kg_cmaes_field_size.argtypes = [vp, cp, C.POINTER(sz)]
-        L.kg_cmaes_get_field.argtypes = [vp, cp, dp, sz]
-        L.kg_cmaes_set_field.argtypes = [vp, cp, dp, sz]
         L.kg_cmaes_get_sorting_index.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.kg_cmaes_get_fields.argtypes = [vp, C.POINTER(cp), sz, dp]
         L.kg_cmaes_wait_termination_fields.argtypes = [vp, dp]
         L.kg_cmaes_set_constraints.argtypes = [vp, CONSTRAINT_FN, vp]
         L.kg_cmaes_prepare_constrained.argtypes = [vp, sz]
         L.kg_cmaes_population_size.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-        L.kg_cmaes_get_rng.argtypes = [vp, ip, vp]
-        L.kg_cmaes_set_rng.argtypes = [vp, ip, vp]
         L.kg_cmaes_device_ptr.argtypes = [vp, cp, C.POINTER(vp)]
         L.kg_cmaes_stream.argtypes = [vp, C.POINTER(vp)]
-        L.kg_cmaes_profile.argtypes = [vp, ip]
-        L.kg_cmaes_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_cmaes_profile_mark.argtypes = [vp, cp, ip]
         L.kg_dea_create.argtypes = [C.POINTER(_DeaCfg), C.POINTER(vp)]
         for f in ("kg_dea_destroy", "kg_dea_initialize", "kg_dea_synchronize"):
@@ -286,14 +288,7 @@ def lib():
         L.kg_dea_generation.argtypes = [vp, sz, ip]
         L.kg_dea_get_candidates.argtypes = [vp, dp, sz]
         L.kg_dea_set_fitness.argtypes = [vp, dp]
-        L.kg_dea_field_size.argtypes = [vp, cp, C.POINTER(sz)]
-        L.kg_dea_get_field.argtypes = [vp, cp, dp, sz]
-        L.kg_dea_set_field.argtypes = [vp, cp, dp, sz]
-        L.kg_dea_get_rng.argtypes = [vp, ip, vp]
-        L.kg_dea_set_rng.argtypes = [vp, ip, vp]
         L.kg_dea_windows.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
-        L.kg_dea_profile.argtypes = [vp, ip]
-        L.kg_dea_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_mocmaes_create.argtypes = [C.POINTER(_MocmaesCfg), C.POINTER(vp)]
         for f in ("kg_mocmaes_destroy", "kg_mocmaes_initialize", "kg_mocmaes_synchronize"):
             getattr(L, f).argtypes = [vp]
@@ -303,14 +298,7 @@ def lib():
         L.kg_mocmaes_generation.argtypes = [vp, sz, ip]
         L.kg_mocmaes_get_candidates.argtypes = [vp, dp, sz]
         L.kg_mocmaes_set_values.argtypes = [vp, dp]
-        L.kg_mocmaes_field_size.argtypes = [vp, cp, C.POINTER(sz)]
-        L.kg_mocmaes_get_field.argtypes = [vp, cp, dp, sz]
-        L.kg_mocmaes_set_field.argtypes = [vp, cp, dp, sz]
-        L.kg_mocmaes_get_rng.argtypes = [vp, ip, vp]
-        L.kg_mocmaes_set_rng.argtypes = [vp, ip, vp]
         L.kg_mocmaes_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 4
-        L.kg_mocmaes_profile.argtypes = [vp, ip]
-        L.kg_mocmaes_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_nested_create.argtypes = [C.POINTER(_NestedCfg), C.POINTER(vp)]
         for f in ("kg_nested_destroy", "kg_nested_first_generation", "kg_nested_eval_builtin", "kg_nested_finalize",
                   "kg_nested_synchronize"):
@@ -320,14 +308,7 @@ def lib():
         L.kg_nested_get_candidates.argtypes = [vp, dp, sz]
         L.kg_nested_set_evaluations.argtypes = [vp, dp]
         L.kg_nested_process.argtypes = [vp, sz, C.POINTER(ip), C.POINTER(ip)]
-        L.kg_nested_field_size.argtypes = [vp, cp, C.POINTER(sz)]
-        L.kg_nested_get_field.argtypes = [vp, cp, dp, sz]
-        L.kg_nested_set_field.argtypes = [vp, cp, dp, sz]
-        L.kg_nested_get_rng.argtypes = [vp, ip, vp]
-        L.kg_nested_set_rng.argtypes = [vp, ip, vp]
         L.kg_nested_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 3
-        L.kg_nested_profile.argtypes = [vp, ip]
-        L.kg_nested_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_nested_permutation.argtypes = [C.c_uint64, sz, C.POINTER(sz)]
         L.kg_mcmc_create.argtypes = [C.POINTER(_McmcCfg), C.POINTER(vp)]
         for f in ("kg_mcmc_destroy", "kg_mcmc_synchronize"):
@@ -338,14 +319,7 @@ def lib():
         L.kg_mcmc_decide.argtypes = [vp, sz, C.c_double, C.POINTER(ip)]
         L.kg_mcmc_end_generation.argtypes = [vp, sz]
         L.kg_mcmc_database.argtypes = [vp, dp, dp, C.POINTER(sz)]
-        L.kg_mcmc_field_size.argtypes = [vp, cp, C.POINTER(sz)]
-        L.kg_mcmc_get_field.argtypes = [vp, cp, dp, sz]
-        L.kg_mcmc_set_field.argtypes = [vp, cp, dp, sz]
-        L.kg_mcmc_get_rng.argtypes = [vp, ip, vp]
-        L.kg_mcmc_set_rng.argtypes = [vp, ip, vp]
         L.kg_mcmc_diagnostics.argtypes = [vp] + [C.POINTER(sz)] * 3
-        L.kg_mcmc_profile.argtypes = [vp, ip]
-        L.kg_mcmc_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         L.kg_tmcmc_create.argtypes = [C.POINTER(_TmcmcCfg), C.POINTER(vp)]
         for f in ("kg_tmcmc_destroy", "kg_tmcmc_synchronize", "kg_tmcmc_evaluate", "kg_tmcmc_evaluate_prior"):
             getattr(L, f).argtypes = [vp]
@@ -354,11 +328,6 @@ def lib():
         for f in ("kg_tmcmc_generation", "kg_tmcmc_prepare", "kg_tmcmc_process", "kg_tmcmc_process_partial",
                   "kg_tmcmc_process_finalize"):
             getattr(L, f).argtypes = [vp, sz]
-        L.kg_tmcmc_field_size.argtypes = [vp, cp, C.POINTER(sz)]
-        L.kg_tmcmc_get_field.argtypes = [vp, cp, dp, sz]
-        L.kg_tmcmc_set_field.argtypes = [vp, cp, dp, sz]
-        L.kg_tmcmc_get_rng.argtypes = [vp, ip, vp]
-        L.kg_tmcmc_set_rng.argtypes = [vp, ip, vp]
         L.kg_tmcmc_get_candidates.argtypes = [vp, dp, sz]
         L.kg_tmcmc_set_evaluations.argtypes = [vp, dp, dp]
         L.kg_tmcmc_set_gradients.argtypes = [vp, dp, dp]
@@ -369,8 +338,6 @@ def lib():
         L.kg_tmcmc_theta_loglik.argtypes = [vp, dp, sz, dp, dp]
         L.kg_tmcmc_advance.argtypes = [vp, sz, C.POINTER(sz)]
         L.kg_tmcmc_get_pending.argtypes = [vp, C.POINTER(C.c_ubyte)]
-        L.kg_tmcmc_profile.argtypes = [vp, ip]
-        L.kg_tmcmc_profile_read.argtypes = [vp, cp, dp, C.POINTER(sz)]
         _LIB = L
     return _LIB
 
@@ -397,8 +364,64 @@ def _vec(x, n, default):
     return a
 
 
-class CmaesDevice:
+class _Handle:
+    """What every solver handle of the C-ABI has under its prefix (kg_dea, ...):
+    destroy, the named fields, the 5000-byte generator states, the stage timer."""
+
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(self._L, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def field_size(self, name):
+        n = C.c_size_t()
+        check(self._fn("_field_size")(self.h, name.encode(), C.byref(n)))
+        return n.value
+
+    def __getitem__(self, name):
+        n = self.field_size(name)
+        out = np.empty(n)
+        check(self._fn("_get_field")(self.h, name.encode(), _dptr(out), n))
+        return out
+
+    def __setitem__(self, name, value):
+        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
+        check(self._fn("_set_field")(self.h, name.encode(), _dptr(a), a.size))
+
+    def _get_rng(self, which):
+        buf = C.create_string_buffer(5000)
+        check(self._fn("_get_rng")(self.h, int(which), buf))
+        return buf.raw
+
+    def _set_rng(self, which, state):
+        assert len(state) == 5000
+        buf = C.create_string_buffer(bytes(state), 5000)
+        check(self._fn("_set_rng")(self.h, int(which), buf))
+
+    def profile(self, enable=True):
+        check(self._fn("_profile")(self.h, int(enable)))
+
+    def profile_read(self, stage):
+        ms, n = C.c_double(), C.c_size_t()
+        check(self._fn("_profile_read")(self.h, stage.encode(), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
+class CmaesDevice(_Handle):
     """One CMA-ES solver instance resident on one MI355X (kg_cmaes_t)."""
+
+    _prefix = "kg_cmaes"
 
     def __init__(self, N, lam, mu=0, mu_type="Logarithmic", lower_bound=None, upper_bound=None, initial_value=None,
                  initial_std=None, min_std_update=None, normal_seed=0, uniform_seed=0, cov_mode="exact",
@@ -478,17 +501,6 @@ class CmaesDevice:
         (kg_cmaes_prepare_constrained); then evaluate the current population."""
         check(self._L.kg_cmaes_prepare_constrained(self.h, int(generation)))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.kg_cmaes_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # stages
     def initialize(self):
         check(self._L.kg_cmaes_initialize(self.h))
@@ -565,22 +577,6 @@ class CmaesDevice:
         F = self._fitness_arg(F)
         check(self._L.kg_cmaes_set_log_posterior(self.h, _dptr(F)))
 
-    # state
-    def field_size(self, name):
-        n = C.c_size_t()
-        check(self._L.kg_cmaes_field_size(self.h, name.encode(), C.byref(n)))
-        return n.value
-
-    def __getitem__(self, name):
-        n = self.field_size(name)
-        out = np.empty(n)
-        check(self._L.kg_cmaes_get_field(self.h, name.encode(), _dptr(out), n))
-        return out
-
-    def __setitem__(self, name, value):
-        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
-        check(self._L.kg_cmaes_set_field(self.h, name.encode(), _dptr(a), a.size))
-
     def get_prefix(self, name, n):
         """The first n doubles of an exchange buffer ("Shard Rows")."""
         out = np.empty(int(n))
@@ -593,14 +589,10 @@ class CmaesDevice:
         return out
 
     def get_rng(self, which):
-        buf = C.create_string_buffer(5000)
-        check(self._L.kg_cmaes_get_rng(self.h, int(which), buf))
-        return buf.raw
+        return self._get_rng(which)
 
     def set_rng(self, which, state):
-        assert len(state) == 5000
-        buf = C.create_string_buffer(bytes(state), 5000)
-        check(self._L.kg_cmaes_set_rng(self.h, int(which), buf))
+        self._set_rng(which, state)
 
     def device_ptr(self, name):
         p = C.c_void_p()
@@ -612,14 +604,6 @@ class CmaesDevice:
         check(self._L.kg_cmaes_stream(self.h, C.byref(p)))
         return p.value
 
-    def profile(self, enable=True):
-        check(self._L.kg_cmaes_profile(self.h, int(enable)))
-
-    def profile_read(self, stage):
-        ms, n = C.c_double(), C.c_size_t()
-        check(self._L.kg_cmaes_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
     def profile_mark(self, stage, phase):
         """kg_cmaes_profile_mark: phase 0 begins, 1 ends a caller-bracketed
         stage on the handle's stream; returns the C-ABI status (1: an end
@@ -627,10 +611,12 @@ class CmaesDevice:
         return int(self._L.kg_cmaes_profile_mark(self.h, stage.encode(), int(phase)))
 
 
-class DeaDevice:
+class DeaDevice(_Handle):
     """One Optimizer/DEA (differential evolution) instance on one MI355X
     (kg_dea_t), bit-exact to the reference's DEA.cpp.base.  Generator indices
     for rng_state / set_rng_state: 0 Normal (kept, never drawn from), 1 Uniform."""
+
+    _prefix = "kg_dea"
 
     def __init__(self, N, P, lower_bound, upper_bound, crossover_rate=0.9, mutation_rate=0.5, mutation_rule="Fixed",
                  parent_rule="Random", accept_rule="Greedy", fix_infeasible=True, normal_seed=0, uniform_seed=0,
@@ -652,17 +638,6 @@ class DeaDevice:
         check(L.kg_dea_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self._L = L
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.kg_dea_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # stages
     def initialize(self):
@@ -697,31 +672,11 @@ class DeaDevice:
             raise ValueError("fitness vector has shape %s, expected (%d,)" % (F.shape, self.P))
         check(self._L.kg_dea_set_fitness(self.h, _dptr(F)))
 
-    # state
-    def field_size(self, name):
-        n = C.c_size_t()
-        check(self._L.kg_dea_field_size(self.h, name.encode(), C.byref(n)))
-        return n.value
-
-    def __getitem__(self, name):
-        n = self.field_size(name)
-        out = np.empty(n)
-        check(self._L.kg_dea_get_field(self.h, name.encode(), _dptr(out), n))
-        return out
-
-    def __setitem__(self, name, value):
-        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
-        check(self._L.kg_dea_set_field(self.h, name.encode(), _dptr(a), a.size))
-
     def rng_state(self, which=1):
-        buf = C.create_string_buffer(5000)
-        check(self._L.kg_dea_get_rng(self.h, int(which), buf))
-        return buf.raw
+        return self._get_rng(which)
 
     def set_rng_state(self, state, which=1):
-        assert len(state) == 5000
-        buf = C.create_string_buffer(bytes(state), 5000)
-        check(self._L.kg_dea_set_rng(self.h, int(which), buf))
+        self._set_rng(which, state)
 
     def windows(self):
         """(windows the last prepare() used, current window size in words)"""
@@ -729,21 +684,15 @@ class DeaDevice:
         check(self._L.kg_dea_windows(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def profile(self, enable=True):
-        check(self._L.kg_dea_profile(self.h, int(enable)))
 
-    def profile_read(self, stage):
-        ms, n = C.c_double(), C.c_size_t()
-        check(self._L.kg_dea_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-
-class MocmaesDevice:
+class MocmaesDevice(_Handle):
     """One Optimizer/MOCMAES (multi-objective CMA-ES) instance on one MI355X
     (kg_mocmaes_t), bit-exact to the reference's MOCMAES.cpp.base.  Generator
     indices for rng_state / set_rng_state: 0 Multinormal, 1 Uniform.
     parent_order "recorded" is the slot order of the reference's committed 2021
     result files, not a Korali setting."""
+
+    _prefix = "kg_mocmaes"
 
     def __init__(self, N, P, lower_bound, upper_bound, mu=0, num_objectives=2, initial_value=None, initial_sdev=None,
                  evolution_path_adaption_strength=-1.0, covariance_learning_rate=-1.0, target_success_rate=0.175,
@@ -773,17 +722,6 @@ class MocmaesDevice:
         # the defaults of setInitialConfiguration (MOCMAES.cpp.base:24-25)
         self.P = int(P) or int(np.ceil(4. + np.floor(3. * np.log(float(self.N)))))
         self.mu = int(mu) or int(self.P / 2.)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.kg_mocmaes_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _objective(objective):
@@ -820,31 +758,11 @@ class MocmaesDevice:
             raise ValueError("value matrix has shape %s, expected (%d, %d)" % (V.shape, self.P, self.K))
         check(self._L.kg_mocmaes_set_values(self.h, _dptr(V)))
 
-    # state
-    def field_size(self, name):
-        n = C.c_size_t()
-        check(self._L.kg_mocmaes_field_size(self.h, name.encode(), C.byref(n)))
-        return n.value
-
-    def __getitem__(self, name):
-        n = self.field_size(name)
-        out = np.empty(n)
-        check(self._L.kg_mocmaes_get_field(self.h, name.encode(), _dptr(out), n))
-        return out
-
-    def __setitem__(self, name, value):
-        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
-        check(self._L.kg_mocmaes_set_field(self.h, name.encode(), _dptr(a), a.size))
-
     def rng_state(self, which=0):
-        buf = C.create_string_buffer(5000)
-        check(self._L.kg_mocmaes_get_rng(self.h, int(which), buf))
-        return buf.raw
+        return self._get_rng(which)
 
     def set_rng_state(self, state, which=0):
-        assert len(state) == 5000
-        buf = C.create_string_buffer(bytes(state), 5000)
-        check(self._L.kg_mocmaes_set_rng(self.h, int(which), buf))
+        self._set_rng(which, state)
 
     def diagnostics(self):
         """(windows the last prepare() used, window size in blocks, archive capacity in rows,
@@ -852,14 +770,6 @@ class MocmaesDevice:
         v = [C.c_size_t() for _ in range(4)]
         check(self._L.kg_mocmaes_diagnostics(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
-
-    def profile(self, enable=True):
-        check(self._L.kg_mocmaes_profile(self.h, int(enable)))
-
-    def profile_read(self, stage):
-        ms, n = C.c_double(), C.c_size_t()
-        check(self._L.kg_mocmaes_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
 
 
 def nested_permutation(seed, n):
@@ -870,7 +780,7 @@ def nested_permutation(seed, n):
     return np.array(out[:int(n)], dtype=np.int64)
 
 
-class NestedDevice:
+class NestedDevice(_Handle):
     """One Sampler/Nested instance (resampling methods Box and Ellipse) on one
     MI355X (kg_nested_t).  prior_min / prior_max are the two parameters of
     every variable's prior, prior_kinds their kinds (PRIOR_KINDS names or
@@ -878,6 +788,8 @@ class NestedDevice:
     needed for the non-Uniform ones.  likelihood: "gaussian", or None when
     the caller sets the log-likelihoods.  Generator indices for rng_state /
     set_rng_state: 0 Normal, 1 Uniform."""
+
+    _prefix = "kg_nested"
 
     def __init__(self, N, L, prior_min, prior_max, batch_size=1, method="Ellipse", add_live_points=True,
                  proposal_update_frequency=1500, ellipsoidal_scaling=1.0, min_log_evidence_delta=0.01,
@@ -912,17 +824,6 @@ class NestedDevice:
         self.h = h
         self._L = lb
         self._rows = self.L
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.kg_nested_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # whole generations, builtin likelihood
     def first_generation(self):
@@ -962,31 +863,11 @@ class NestedDevice:
     def synchronize(self):
         check(self._L.kg_nested_synchronize(self.h))
 
-    # state
-    def field_size(self, name):
-        n = C.c_size_t()
-        check(self._L.kg_nested_field_size(self.h, name.encode(), C.byref(n)))
-        return n.value
-
-    def __getitem__(self, name):
-        n = self.field_size(name)
-        out = np.empty(n)
-        check(self._L.kg_nested_get_field(self.h, name.encode(), _dptr(out), n))
-        return out
-
-    def __setitem__(self, name, value):
-        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
-        check(self._L.kg_nested_set_field(self.h, name.encode(), _dptr(a), a.size))
-
     def rng_state(self, which=0):
-        buf = C.create_string_buffer(5000)
-        check(self._L.kg_nested_get_rng(self.h, int(which), buf))
-        return buf.raw
+        return self._get_rng(which)
 
     def set_rng_state(self, state, which=0):
-        assert len(state) == 5000
-        buf = C.create_string_buffer(bytes(state), 5000)
-        check(self._L.kg_nested_set_rng(self.h, int(which), buf))
+        self._set_rng(which, state)
 
     def diagnostics(self):
         """(windows the last candidate draw used, tries it consumed, current window size in tries)"""
@@ -994,22 +875,16 @@ class NestedDevice:
         check(self._L.kg_nested_diagnostics(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
-    def profile(self, enable=True):
-        check(self._L.kg_nested_profile(self.h, int(enable)))
 
-    def profile_read(self, stage):
-        ms, n = C.c_double(), C.c_size_t()
-        check(self._L.kg_nested_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-
-class McmcDevice:
+class McmcDevice(_Handle):
     """One Sampler/MCMC chain (Metropolis-Hastings with delayed rejection and
     adaptive sampling) on one MI355X (kg_mcmc_t).  probability: "gaussian", or
     None when the caller evaluates logP(x) (the stepping methods).  With
     prior_kinds (PRIOR_KINDS names or numbers; prior_min / prior_max their two
     parameters) logP = logPrior + the kernel's or the caller's value.
     Generator indices for rng_state / set_rng_state: 0 Normal, 1 Uniform."""
+
+    _prefix = "kg_mcmc"
 
     def __init__(self, N, initial_mean, initial_sdev, burn_in=0, leap=1, rejection_levels=1,
                  use_adaptive_sampling=False, non_adaption_period=0, chain_covariance_scaling=1.0, max_samples=5000,
@@ -1040,17 +915,6 @@ class McmcDevice:
         check(lb.kg_mcmc_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self._L = lb
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.kg_mcmc_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # whole generations, builtin kernel
     def run(self, first_generation, count, max_model_evaluations=0):
@@ -1099,31 +963,11 @@ class McmcDevice:
     def synchronize(self):
         check(self._L.kg_mcmc_synchronize(self.h))
 
-    # state
-    def field_size(self, name):
-        n = C.c_size_t()
-        check(self._L.kg_mcmc_field_size(self.h, name.encode(), C.byref(n)))
-        return n.value
-
-    def __getitem__(self, name):
-        n = self.field_size(name)
-        out = np.empty(n)
-        check(self._L.kg_mcmc_get_field(self.h, name.encode(), _dptr(out), n))
-        return out
-
-    def __setitem__(self, name, value):
-        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
-        check(self._L.kg_mcmc_set_field(self.h, name.encode(), _dptr(a), a.size))
-
     def rng_state(self, which=0):
-        buf = C.create_string_buffer(5000)
-        check(self._L.kg_mcmc_get_rng(self.h, int(which), buf))
-        return buf.raw
+        return self._get_rng(which)
 
     def set_rng_state(self, state, which=0):
-        assert len(state) == 5000
-        buf = C.create_string_buffer(bytes(state), 5000)
-        check(self._L.kg_mcmc_set_rng(self.h, int(which), buf))
+        self._set_rng(which, state)
 
     def diagnostics(self):
         """(launches the last run used, relaunches after an exhausted window, window size in candidates)"""
@@ -1131,16 +975,8 @@ class McmcDevice:
         check(self._L.kg_mcmc_diagnostics(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
-    def profile(self, enable=True):
-        check(self._L.kg_mcmc_profile(self.h, int(enable)))
 
-    def profile_read(self, stage):
-        ms, n = C.c_double(), C.c_size_t()
-        check(self._L.kg_mcmc_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
-
-
-class TmcmcDevice:
+class TmcmcDevice(_Handle):
     """One TMCMC sampler instance (Version "TMCMC") on one MI355X (kg_tmcmc_t).
 
     prior_min / prior_max: the Univariate/Uniform prior of every variable
@@ -1149,6 +985,8 @@ class TmcmcDevice:
     from (variables sharing a distribution share its generator); prior_seeds[k]:
     seed of distribution k.  Generator indices for get_rng / set_rng:
     0 Multinomial, 1 Multivariate, 2 Uniform, 3 + k prior distribution k."""
+
+    _prefix = "kg_tmcmc"
 
     def __init__(self, N, P, prior_min, prior_max, prior_seeds=None, prior_distribution=None,
                  multinomial_seed=0, multivariate_seed=0, uniform_seed=0, target_cov=1.0, covariance_scaling=0.04,
@@ -1188,17 +1026,6 @@ class TmcmcDevice:
         check(L.kg_tmcmc_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self._L = L
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.kg_tmcmc_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def prepare(self, generation):
         check(self._L.kg_tmcmc_prepare(self.h, int(generation)))
@@ -1359,35 +1186,8 @@ class TmcmcDevice:
                                             _dptr(out)))
         return out
 
-    def field_size(self, name):
-        n = C.c_size_t()
-        check(self._L.kg_tmcmc_field_size(self.h, name.encode(), C.byref(n)))
-        return n.value
-
-    def __getitem__(self, name):
-        n = self.field_size(name)
-        out = np.empty(n)
-        check(self._L.kg_tmcmc_get_field(self.h, name.encode(), _dptr(out), n))
-        return out
-
-    def __setitem__(self, name, value):
-        a = np.ascontiguousarray(np.asarray(value, dtype=np.float64).reshape(-1))
-        check(self._L.kg_tmcmc_set_field(self.h, name.encode(), _dptr(a), a.size))
-
     def get_rng(self, which):
-        buf = C.create_string_buffer(5000)
-        check(self._L.kg_tmcmc_get_rng(self.h, int(which), buf))
-        return buf.raw
+        return self._get_rng(which)
 
     def set_rng(self, which, state):
-        assert len(state) == 5000
-        buf = C.create_string_buffer(bytes(state), 5000)
-        check(self._L.kg_tmcmc_set_rng(self.h, int(which), buf))
-
-    def profile(self, enable=True):
-        check(self._L.kg_tmcmc_profile(self.h, int(enable)))
-
-    def profile_read(self, stage):
-        ms, n = C.c_double(), C.c_size_t()
-        check(self._L.kg_tmcmc_profile_read(self.h, stage.encode(), C.byref(ms), C.byref(n)))
-        return ms.value, n.value
+        self._set_rng(which, state)
